@@ -19,6 +19,11 @@ collective); the weak-scaling job (every rank its own 20,000-simulation sweep,
 seeds 50r..50r+49) is timed after it and reported as `weak_scaling`
 (--scaling weak makes it the headline instead).
 
+A plain run sets up, warms up, times --steps steps and prints the headline line.  Everything
+that takes runs of its own -- the CPU baselines, the C5 and fp64 lines under `secondary`, the
+weak-scaling job -- runs only with --full.  --dump-outputs DIR writes what the last timed step
+left (dump_outputs below) as DIR/<name>.npy, for comparing two builds output for output.
+
 Prints ONE JSON line (rank 0).
 """
 import argparse
@@ -175,9 +180,66 @@ def cpu_baseline(sc, seconds=8.0, steps=2000, numpy_leg=True):
     return best
 
 
-def run_workload(sc, G, S, keys, p, args, dev, dist, steps, warmup):
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs writes at most this much in all
+DUMP_SEED = 0
+
+
+def dump_outputs(path, bt, ring, tmaj, bold, welch, slot, SLOT, LD):
+    """What a caller of the timed path holds after its last step, as path/<name>.npy (float32 or
+    float64), for a fixed seeded sample of simulations (the whole arrays are tens of GB):
+      sims_state, sims_rec   the sampled simulation indices (of this rank's shard), ascending
+      E, I, a_ie             integrator state [len(sims_state)][N]
+      welch_acc              node-summed Welch accumulator [len(sims_state)][bins]
+      bold_state             Balloon (s, f, v, q) and forward band-pass state of the BOLD stream
+                             [8][len(sims_state) * N]
+      rec_E                  the step's recorded E [SLOT][len(sims_rec) * N], time-major, as the
+                             integrator wrote it
+      ring_E                 the same samples in the node-major Welch ring (fp32: the BOLD pass's
+                             transposed copy; fp64: the integrator's own record, = rec_E)
+    slot is the ring slot of the last step (None: no step ran, nothing recorded)."""
+    B, N = bt.B, bt.N
+    C = B * N
+    rng = np.random.default_rng(DUMP_SEED)
+    order = rng.permutation(B)
+    sims_state = np.sort(order[:max(1, min(B, 1024, 92160 // N))])
+    sims_rec = np.sort(order[:max(1, min(B, 1440 // N))])
+
+    def cols(sims):
+        return torch.from_numpy((sims[:, None] * N + np.arange(N)[None, :]).ravel()).to(bt.device)
+
+    i_state = torch.from_numpy(sims_state).to(bt.device)
+    out = {"sims_state": sims_state.astype(np.float64), "sims_rec": sims_rec.astype(np.float64)}
+    for name, t in (("E", bt.E), ("I", bt.I), ("a_ie", bt.A)):
+        out[name] = t.reshape(B, N)[i_state]
+    if welch is not None:
+        out["welch_acc"] = welch.acc[i_state]
+    if bold is not None:
+        out["bold_state"] = bold.state[:8 * C].view(8, C)[:, cols(sims_state)]
+    if slot is not None:
+        c_rec = cols(sims_rec)
+        rows = ring.view(C, LD)[c_rec, slot * SLOT:(slot + 1) * SLOT].t()
+        if tmaj is not None:
+            out["rec_E"] = tmaj.view(SLOT, C)[:, c_rec]
+            if bold is not None:
+                out["ring_E"] = rows
+        else:
+            out["rec_E"] = out["ring_E"] = rows
+    os.makedirs(path, exist_ok=True)
+    total = 0
+    for name, a in out.items():
+        if torch.is_tensor(a):
+            a = a.contiguous().cpu().numpy()
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        total += a.nbytes
+        assert total <= DUMP_MAX_BYTES, f"--dump-outputs: {name} brings the dump to {total} bytes"
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
+
+
+def run_workload(sc, G, S, keys, p, args, dev, dist, steps, warmup, dump=None):
     """Time `steps` bench steps of one batch after `warmup` untimed ones; a barrier and a device
-    synchronisation on both sides, the maximum over ranks.  -> (seconds, mean ms per kernel)."""
+    synchronisation on both sides, the maximum over ranks.  dump: a directory for dump_outputs,
+    written after the clock stops.  -> (seconds, mean ms per kernel)."""
     from nremmodfc_amd.sigchain import NEQ, BoldStream, WelchAccumulator
 
     N = sc.shape[0]
@@ -276,10 +338,13 @@ def run_workload(sc, G, S, keys, p, args, dev, dist, steps, warmup):
     if kern["bold"] is not None:
         kern["bold"] /= CHUNKS  # ms per 1000-sample chunk (each pass takes a step's two)
     kern.pop("welch1")  # (a lone last segment of an odd step count: timed in the step, not reported)
+    if dump:
+        last = (state["k"] // CHUNKS - 1) % NSLOT if state["k"] else None
+        dump_outputs(dump, bt, ring, tmaj, bold, welch, last, SLOT, LD)
     return elapsed, kern
 
 
-def measure(args, world, rank, local, dist, cpu_seconds=None, cpu_numpy=True):
+def measure(args, world, rank, local, dist, cpu_seconds=None, cpu_numpy=True, dump=None):
     """One bench line for args.config / args.precision: time the workload, attach the roofline, and
     (rank 0 of a one-GPU run, cpu_seconds given) the CPU baseline of the same workload."""
     if args.scaling is None:  # c3: the ONE sweep north_star names, split over the ranks (identical at N = 1)
@@ -303,7 +368,7 @@ def measure(args, world, rank, local, dist, cpu_seconds=None, cpu_numpy=True):
     B = len(keys)
     p = driver_params()
     dev = torch.device("cuda", local)
-    elapsed, kern = run_workload(sc, G, S, keys, p, args, dev, dist, args.steps, args.warmup)
+    elapsed, kern = run_workload(sc, G, S, keys, p, args, dev, dist, args.steps, args.warmup, dump=dump)
     weak = None
     if dist and args.scaling == "strong" and args.config == "c3" and args.weak_steps > 0:
         # the weak-scaling aggregate beside it: every rank its own 20,000-simulation sweep (seeds 50r..)
@@ -501,7 +566,13 @@ def main():
                          "synthetic connectome, 2,500 sims per GPU (20,000 over 8 GPUs)")
     ap.add_argument("--sde-only", action="store_true",
                     help="time the integrator alone (no streamed BOLD / Welch consumers)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: the CPU baselines (cpu_baseline), the C5 "
+                         "and fp64 lines (secondary) and, with N > 1 ranks, the weak-scaling job (weak_scaling)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one left (rank 0's shard; a fixed seeded "
+                         "sample of simulations, at most 64 MB) as DIR/<name>.npy: see dump_outputs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--dist-backend", default="nccl", choices=("nccl", "gloo"),
                     help="nccl (RCCL, one GPU per rank); gloo only to rehearse several ranks on one GPU")
     ap.add_argument("--cpu-seconds", type=float, default=8.0)
@@ -510,10 +581,10 @@ def main():
                          "GPUs = 2,500 x 8) split round-robin over the ranks; weak (the c5 default): 20,000 (c3) / "
                          "2,500 (c5) sims per rank")
     ap.add_argument("--secondary-steps", type=int, default=2,
-                    help="the default c3 f32 line also times the C5 (1000-node) and the fp64 (reference precision) "
+                    help="with --full the default c3 f32 line also times the C5 (1000-node) and the fp64 (reference precision) "
                          "workloads for this many steps each, reported under `secondary` (0: skip)")
     ap.add_argument("--weak-steps", type=int, default=2,
-                    help="c3, strong, N > 1: also time this many steps of the weak-scaling job (every rank its "
+                    help="with --full, c3, strong, N > 1: also time this many steps of the weak-scaling job (every rank its "
                          "own 20,000-sim sweep) and report its aggregate as weak_scaling (0: skip)")
     args = ap.parse_args()
 
@@ -531,8 +602,13 @@ def main():
         else:
             dist.init_process_group("gloo")
 
-    out = measure(args, world, rank, local, dist, None if args.no_cpu_baseline else args.cpu_seconds)
-    if args.config == "c3" and args.precision == "f32" and not args.sde_only and args.secondary_steps > 0:
+    cpu = args.full and not args.no_cpu_baseline
+    if not args.full:
+        args.weak_steps = 0
+    out = measure(args, world, rank, local, dist, args.cpu_seconds if cpu else None,
+                  dump=args.dump_outputs if rank == 0 else None)
+    if args.full and args.config == "c3" and args.precision == "f32" and not args.sde_only \
+            and args.secondary_steps > 0:
         # north_star asks for the 1000-node throughput and the reference-precision line beside the
         # headline: both timed in the same run, each with its own roofline, kernel times and CPU baseline
         sec = {}
@@ -541,8 +617,7 @@ def main():
             a2.config, a2.precision, a2.scaling, a2.weak_steps = cfg, prec, None, 0
             a2.steps, a2.warmup = args.secondary_steps, 1
             torch.cuda.empty_cache()
-            r = measure(a2, world, rank, local, dist,
-                        None if args.no_cpu_baseline else args.cpu_seconds / 2, cpu_numpy=(cfg == "c5"))
+            r = measure(a2, world, rank, local, dist, args.cpu_seconds / 2 if cpu else None, cpu_numpy=(cfg == "c5"))
             sec[name] = {k: r[k] for k in ("metric", "value", "unit", "steps", "warmup", "ms_per_step", "scaling",
                                            "dtype", "dtype_detail", "data", "config", "roofline", "kernel_ms",
                                            "cpu_baseline")}

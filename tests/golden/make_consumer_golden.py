@@ -229,7 +229,9 @@ def main():
             out["c2_homo__fig4_matts_sha256"] = np.array(array_digest(m))
         else:
             out[f"c2_{mod}__fig4_matts"] = m
-    np.savez_compressed(os.path.join(HERE, "consumer_golden.npz"), **out)
+    sys.path.insert(0, ROOT)
+    from tests.golden import save_parts
+    save_parts(os.path.join(HERE, "consumer_golden.npz"), **out)  # (in parts: no committed file above 1 MiB)
     print("c2 digests", out["c2_homo__digest"], out["c2_map__digest"], out["c2_shuf__digest"])
 
 

@@ -3,8 +3,9 @@
 CPU: the cpu_baseline legs (the compiled C port, the cost of the reference's numba-compiled loop,
 as the value; the interpreted NumPy loop, oracle/numpy_run.py, one process per core, beside it)
 on a short sample.
-GPU: one short bench run as a child process; its single JSON line carries every
-contract key, the roofline and issued-MFMA objects, and consistent arithmetic.
+GPU: one short `--full` bench run as a child process; its single JSON line carries every
+contract key, the roofline and issued-MFMA objects, and consistent arithmetic.  A plain run
+(no --full) prints the headline alone and, with --dump-outputs, writes the last step's outputs.
 """
 import json
 import os
@@ -53,7 +54,7 @@ def test_pmc_stamp_is_the_loaded_library():
 
 @pytest.mark.gpu
 def test_bench_json_contract(cuda):
-    out = subprocess.run([sys.executable, "bench.py", "--steps", "1", "--warmup", "1", "--cpu-seconds", "1",
+    out = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "1", "--warmup", "1", "--cpu-seconds", "1",
                           "--secondary-steps", "2"], cwd=ROOT, capture_output=True, text=True, timeout=180)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -85,7 +86,7 @@ def test_bench_json_contract(cuda):
 
 @pytest.mark.gpu
 def test_bench_c5_line_priced_on_mfma(cuda):
-    out = subprocess.run([sys.executable, "bench.py", "--config", "c5", "--steps", "1", "--warmup", "0",
+    out = subprocess.run([sys.executable, "bench.py", "--full", "--config", "c5", "--steps", "1", "--warmup", "0",
                           "--sde-only", "--cpu-seconds", "1"], cwd=ROOT, capture_output=True, text=True, timeout=150)
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][0])
@@ -101,3 +102,38 @@ def test_bench_c5_line_priced_on_mfma(cuda):
     assert d["cpu_baseline"]["value"] > 0 and "N=1000" in d["cpu_baseline"]["sample"]
     # counters are attached only when taken on the library this run loaded
     assert r["pmc"] is None or r["pmc_lib_sha256"] is not None
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_lean_and_dumps_outputs(cuda, tmp_path):
+    """A plain run times the headline only (no CPU baseline, no secondary lines) and --dump-outputs
+    leaves the last timed step's outputs as float32 / float64 .npy files of at most 64 MB in all."""
+    import numpy as np
+    dump = tmp_path / "dump"
+    out = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1",
+                          "--dump-outputs", str(dump)], cwd=ROOT, capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["cpu_baseline"] is None and "secondary" not in d and d["weak_scaling"] is None
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["dtype"].startswith("f32") and d["higher_is_better"] is True
+    assert d["metric"].startswith("node-timesteps/sec") and d["unit"] == "node-timesteps/sec"
+    ns = d["config"]["sims_per_gpu"] * d["config"]["nodes"] * d["config"]["euler_steps_per_step"] * d["steps"]
+    assert d["ms_per_step"] > 0 and abs(ns / (d["ms_per_step"] * 1e-3 * d["steps"]) / d["value"] - 1) < 1e-6
+    # three steps: two integrator launches each, one BOLD pass each, and the Welch segments of the
+    # timed steps (a launch of two, then the odd step's one alone)
+    assert d["kernel_ms"]["sde"] > 0 and d["kernel_ms"]["bold"] > 0 and d["kernel_ms"]["welch"] > 0
+    a = {f[:-4]: np.load(dump / f) for f in sorted(os.listdir(dump))}
+    assert set(a) == {"sims_state", "sims_rec", "E", "I", "a_ie", "welch_acc", "bold_state", "rec_E", "ring_E"}
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    assert all(np.isfinite(v).all() for v in a.values())
+    ns_, nr, N = len(a["sims_state"]), len(a["sims_rec"]), 90
+    assert a["E"].shape == a["I"].shape == a["a_ie"].shape == (ns_, N) and a["welch_acc"].shape[0] == ns_
+    assert a["bold_state"].shape == (8, ns_ * N) and a["rec_E"].shape == (2000, nr * N)
+    assert a["rec_E"].dtype == np.float32 and np.ptp(a["rec_E"]) > 0
+    # the BOLD pass's node-major copy in the Welch ring is the integrator's record, transposed
+    np.testing.assert_array_equal(a["ring_E"], a["rec_E"])
+    assert (a["welch_acc"] >= 0).all() and a["welch_acc"].max() > 0
+    assert np.ptp(a["E"]) > 0 and set(a["sims_rec"]) <= set(a["sims_state"])

@@ -26,6 +26,7 @@ import numpy as np
 import pandas as pd
 import pytest
 
+from tests.golden import load_parts
 from tests.golden.make_consumer_golden import array_digest, pickle_digest, sha256
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -123,7 +124,7 @@ def load_many_seeds(dic, nseeds=None):
 
 
 def _check_extract_equals_reference(path, prefix, fn=extract):
-    g = np.load(GOLD)
+    g = load_parts(GOLD)
     assert sha256(path) == str(g[f"{prefix}__sha256"]), f"{path} is not the input the reference's extract() read"
     ours = fn(pd.read_csv(path))
     np.testing.assert_array_equal(ours["x_vals"], g[f"{prefix}__x_vals"])
@@ -165,7 +166,7 @@ def test_fig3_extract_and_statistics_equal_reference():
     the same inputs exactly.  On the build's tables, as on the shipped ones, every homo-vs-map and
     shuffled-vs-map difference of the optima's seed distributions is significant after the FDR step
     (restated, statsmodels absent) with the same sign of Cohen's d."""
-    g = np.load(GOLD)
+    g = load_parts(GOLD)
     adj = {}
     for which, paths in (("shipped", (SHIPPED, SHIPPED_MAPS, SHIPPED_SHUF)),
                          ("product", (PRODUCT, PRODUCT_MAPS, PRODUCT_SHUF))):
@@ -184,7 +185,7 @@ def test_heatmaps_of_this_builds_sweep_track_the_shipped_ones():
     """The reference's extract() output on the build's table against its output on the shipped
     table (both from consumer_golden.npz): the same axes, cell maps correlated > 0.99, the same W
     optimum; the sleep states' optima lie on a flat valley (within 5% of the shipped optimum's value)."""
-    g = np.load(GOLD)
+    g = load_parts(GOLD)
     np.testing.assert_array_equal(g["product_homo__x_vals"], g["shipped_homo__x_vals"])
     np.testing.assert_array_equal(g["product_homo__y_vals"], g["shipped_homo__y_vals"])
     for k, st in enumerate(STATES + ("mean", "sync", "meta")):
@@ -233,7 +234,7 @@ def test_c2_pickle_regenerates_and_loads_like_the_reference(c2_pickles):
     contents equal the pickle the reference's loaders read when the fixture was made (sha256 of
     every array), and the restated loaders give the reference's matts / Hin_nodes / Hse_nodes."""
     d = c2_pickles["homo"]
-    g = np.load(GOLD)
+    g = load_parts(GOLD)
     assert pickle_digest(d) == str(g["c2_homo__digest"])
     for tag, nseeds in (("asm", None), ("fig5", 50)):
         matts, hin, hse = load_many_seeds(d, nseeds)
@@ -248,7 +249,7 @@ def test_c2_map_and_shuffled_pickles_load_like_fig4(c2_pickles):
     the map and shuffled ones with the homo pickle's keys: the regenerated map and shuffled pickles
     equal the ones the reference's Fig4 statements read (digests), share the homo pickle's keys, and
     the restated loop gives the reference's seed-mean FCs exactly."""
-    g = np.load(GOLD)
+    g = load_parts(GOLD)
     for mod in ("map", "shuf"):
         assert pickle_digest(c2_pickles[mod]) == str(g[f"c2_{mod}__digest"])
         assert set(c2_pickles[mod]) == set(c2_pickles["homo"])

@@ -14,6 +14,7 @@ import os
 import numpy as np
 
 import oracle.sigchain as osg
+from tests.golden import load_parts
 
 G = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
@@ -27,14 +28,14 @@ def _full(flat, n=90):
 
 
 def test_fixture_oracle_rows_equal_the_pinned_rows():
-    fx = np.load(os.path.join(G, "ref_replay_full.npz"))
+    fx = load_parts(os.path.join(G, "ref_replay_full.npz"))
     pin = json.load(open(os.path.join(G, "oracle_pin_cell.json")))
     assert list(fx["columns"]) == pin["columns"] and list(fx["seeds"]) == pin["seeds"]
     np.testing.assert_array_equal(fx["m_orc"], np.array(pin["rows"]))
 
 
 def test_reference_rows_match_the_shipped_table():
-    fx = np.load(os.path.join(G, "ref_replay_full.npz"))
+    fx = load_parts(os.path.join(G, "ref_replay_full.npz"))
     st = np.load(os.path.join(G, "shipped_cell_stats.npz"))
     k = [tuple(np.round(c, 4)) for c in st["homo_cells"]].index((0.0, 0.0))
     vals, n = fx["m_ref"], len(fx["m_ref"])
@@ -44,7 +45,7 @@ def test_reference_rows_match_the_shipped_table():
 
 
 def test_same_noise_floor_of_two_fp64_implementations():
-    fx = np.load(os.path.join(G, "ref_replay_full.npz"))
+    fx = load_parts(os.path.join(G, "ref_replay_full.npz"))
     ref = [_full(f) for f in fx["fc_ref"]]
     orc = [_full(f) for f in fx["fc_orc"]]
     same = np.array([osg.ssim(a, b, 1.0) for a, b in zip(ref, orc)])

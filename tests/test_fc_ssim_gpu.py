@@ -28,6 +28,7 @@ import oracle.sigchain as osg
 from nremmodfc_amd import datasets, sweep
 from nremmodfc_amd.model import Schedule
 from nremmodfc_amd.pipeline import run_sweep
+from tests.golden import load_parts
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_replay_full.npz")
@@ -43,7 +44,7 @@ def _full(flat, n=90):
 
 
 def test_fc_same_seed_full_horizon_vs_reference_run(cuda, sc90):
-    fx = np.load(GOLD)
+    fx = load_parts(GOLD)
     keys = fx["keys"][:K].astype(np.uint64)
     ref = np.stack([_full(f) for f in fx["fc_ref"][:K]])
     orc = np.stack([_full(f) for f in fx["fc_orc"][:K]])

@@ -28,6 +28,7 @@ sys.path.insert(0, ROOT)
 from nremmodfc_amd import datasets, sweep  # noqa: E402
 from nremmodfc_amd.model import Schedule, driver_params  # noqa: E402
 from nremmodfc_amd.pipeline import run_sweep  # noqa: E402
+from tests.golden import load_parts  # noqa: E402
 
 EPS = (1e-15, 1e-12, 1e-9, 1e-6)
 
@@ -39,7 +40,7 @@ def flat(fc):
 
 def main():
     out = sys.argv[1]
-    fx = np.load(os.path.join(ROOT, "tests", "golden", "ref_replay_full.npz"))
+    fx = load_parts(os.path.join(ROOT, "tests", "golden", "ref_replay_full.npz"))
     keys = fx["keys"].astype(np.uint64)
     K, N = len(keys), 90
     sc = datasets.load_sc()

@@ -89,7 +89,8 @@ def main():
                                            if s < len(r["div"])},
                               "t_ref": round(r["t_ref"], 1), "t_orc": round(r["t_orc"], 1)}), flush=True)
     out = OUT if not os.environ.get("WCSDE_HORIZON_TEST") else "/tmp/ref_replay_test.npz"
-    np.savez_compressed(
+    from tests.golden import save_parts
+    save_parts(  # (in parts: no committed file above 1 MiB)
         out, seeds=np.array([r["seed"] for r in res]), streams=np.array([r["stream"] for r in res]),
         keys=np.array([r["key"] for r in res], dtype=np.uint64),
         fc_ref=np.stack([r["fc_ref"] for r in res]), fc_orc=np.stack([r["fc_orc"] for r in res]),

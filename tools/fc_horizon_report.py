@@ -20,6 +20,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import oracle.sigchain as osg  # noqa: E402
+from tests.golden import load_parts  # noqa: E402
 
 N = 90
 
@@ -41,7 +42,7 @@ def stats(x):
 
 
 def main():
-    fx = np.load(os.path.join(ROOT, "tests", "golden", "ref_replay_full.npz"))
+    fx = load_parts(os.path.join(ROOT, "tests", "golden", "ref_replay_full.npz"))
     g = np.load(sys.argv[1])
     out_path = sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "profiles", "r03_fc_horizon.json")
     assert np.array_equal(fx["keys"], g["keys"])

@@ -3,7 +3,7 @@
 # reference-precision bench (bench64), the full homogeneous sweep with its statistics against the
 # shipped table (sweep) and the CPU baseline against core count (cpu).
 #   STEPS="tests smoke bench prof trace pmc bench64 sweep many shards c4shards c5sweep cpu" bash tools/gpu_check.sh
-#   trace: kernel trace + stats of the default bench command (C3 + its C5 and fp64 secondary lines;
+#   trace: kernel trace + stats of the default --full bench command (C3 + its C5 and fp64 secondary lines;
 #          the C5 kernel as an ordinary launch, WCSDE_COOP=0: rocprofv3's teardown faults after a
 #          cooperative one)
 #   pmc:   every counter set bench.py attaches (tools/profile_bench.sh, profile_f64.sh, profile_c5_all.sh),
@@ -30,11 +30,11 @@ for s in $STEPS; do
       echo "smoke rc=$rc"; tail -5 $OUT/smoke.log
       if [ $rc -ne 0 ]; then echo "STOP after smoke"; exit $rc; fi ;;
     bench)
-      timeout -k 10 600 python bench.py ${BENCH_ARGS:-} > $OUT/bench.log 2>&1; rc=$?
+      timeout -k 10 600 python bench.py --full ${BENCH_ARGS:-} > $OUT/bench.log 2>&1; rc=$?
       echo "bench rc=$rc"; tail -5 $OUT/bench.log
       if [ $rc -ne 0 ]; then echo "STOP after bench"; exit $rc; fi ;;
     prof)
-      timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o sde -- python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline > $OUT/prof.log 2>&1; rc=$?
+      timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o sde -- python3 bench.py --full --steps 5 --warmup 1 --no-cpu-baseline > $OUT/prof.log 2>&1; rc=$?
       echo "prof rc=$rc"; tail -3 $OUT/prof.log; find $OUT/prof -name "*stats*" | head
       if [ $rc -ne 0 ]; then echo "STOP after prof"; exit $rc; fi ;;
     bench64)
@@ -55,7 +55,7 @@ for s in $STEPS; do
       echo "many rc=$rc"; tail -1 $OUT/many.log | cut -c1-300
       if [ $rc -ne 0 ]; then echo "STOP after many"; exit $rc; fi ;;
     trace)
-      WCSDE_COOP=0 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o bench -- python3 bench.py --no-cpu-baseline > $OUT/trace.log 2>&1; rc=$?
+      WCSDE_COOP=0 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o bench -- python3 bench.py --full --no-cpu-baseline > $OUT/trace.log 2>&1; rc=$?
       echo "trace rc=$rc"; grep '^{' $OUT/trace.log | cut -c1-200
       find $OUT/trace -name "*kernel_trace.csv" -size +10M -delete
       if [ $rc -ne 0 ]; then echo "STOP after trace"; exit $rc; fi ;;
