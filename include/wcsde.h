@@ -242,9 +242,24 @@ int wc_filtfilt(int order, const double* b, const double* a, const double* zi, i
 
 /* Unit phasors exp(i angle(hilbert(x, axis=0))) of every column of x [M][C]
  * (utils.kuramoto, utils.py:35-37): phasor [M][C][2] (cos, sin).  workspace:
- * >= M doubles. */
+ * >= M doubles.  Range: 2 <= M <= 8192.  It is a direct circulant convolution,
+ * O(M^2) per column, with the length-M Hilbert kernel in LDS (M * 8 bytes of a
+ * 64 KB launch); longer series return WC_EUNSUPPORTED: use wc_hilbert_phase_long. */
 int wc_hilbert_phase(int64_t C, int M, const double* x, double* phasor, void* workspace,
                      size_t ws_bytes, void* stream);
+
+/* The same phasors for long series, 2 <= M <= 524288, in O(M log M): the exact
+ * length-M DFT and its inverse (scipy.signal.hilbert pads nothing) as Bluestein
+ * convolutions over a power-of-two FFT of length L = max(2^15, nextpow2(2 M - 1))
+ * (wc_hilbert.hip).  phasor [M][C][2] as above (16-byte aligned, as workspace).
+ * wc_hilbert_long_workspace_size is the minimum: the tables (W_1024, the chirp
+ * and its spectrum) and two [L] complex buffers for one column; every further
+ * 32 L bytes let one more column be in flight per pass (up to C), and the result
+ * is bit-identical for every workspace size and every C.  0 for C <= 0, M < 2 or
+ * M > 524288 (wc_hilbert_phase_long then returns WC_EINVAL / WC_EUNSUPPORTED). */
+size_t wc_hilbert_long_workspace_size(int64_t C, int64_t M);
+int wc_hilbert_phase_long(int64_t C, int64_t M, const double* x, double* phasor, void* workspace,
+                          size_t ws_bytes, void* stream);
 
 /* Per simulation b of bold [M][B][N] (the filtered, decimated BOLD; or, with
  * bold == NULL, of the given fc_in [B][N][N]):

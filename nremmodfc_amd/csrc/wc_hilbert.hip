@@ -1,0 +1,391 @@
+// wc_hilbert.hip -- Hilbert phases of long series (gfx950): utils.kuramoto's
+// scipy.signal.hilbert(x, axis=0) for 2 <= M <= 524,288 samples per column.
+//
+// The analytic signal needs the exact length-M DFT (scipy pads nothing), and M is
+// arbitrary (cortex_run.py's BOLD has 29,800 = 2^3 5^2 149 samples), so both DFTs
+// are Bluestein convolutions over a power-of-two FFT of length
+//   L = max(2^15, nextpow2(2 M - 1)):
+//   X[k] = w[k] sum_n (x[n] w[n]) conj(w)[k - n],  w[k] = exp(-i pi k^2 / M),
+// with k^2 reduced mod 2 M in integers before sincospi.  The inverse DFT is
+// conj(DFT(conj(.))) / M, so one chirp and one chirp spectrum serve both.
+//
+// FFT_L is a four-step L = L1 L2 (n = L2 n1 + n2, k = k1 + L1 k2; L1, L2 <= 1024):
+//   column pass: L1-point FFTs over n1 (stride L2), times W_L^(n2 k1)
+//   row pass:    L2-point FFTs over n2 (contiguous)
+// which leaves X[k1 + L1 k2] at position k1 L2 + k2.  A convolution does not care:
+// the chirp spectrum is stored in the same order and the inverse runs the two
+// passes backwards (rows, conjugate twiddle, columns) and lands in natural order.
+// Passes that work on the same points are fused, so a column tile makes five trips
+// through memory:
+//   1. col  x w, zero padded -> FFT_L1, twiddle
+//   2. row  FFT_L2, times the chirp spectrum, IFFT_L2, conjugate twiddle
+//   3. col  IFFT_L1 -> conj(c) h / L (= conj(X h) w: the second DFT's input) -> FFT_L1, twiddle
+//   4. row  as 2
+//   5. col  IFFT_L1 -> conj(w) . = the analytic signal (up to a positive scale) -> unit phasor
+// Work buffers are [L][tc] complex for a tile of tc columns (the columns of one
+// point are contiguous), two of them, each pass reading one and writing the other.
+// A workgroup (512 threads) owns 4096 points in LDS: G = 4096 / N sub-FFTs of length
+// N, i.e. G neighbouring (n2, c) or (k1, c) items, whose points are G * 16
+// contiguous bytes in memory.  The sub-FFT is an in-place Stockham (every read of a
+// stage, barrier, every write, barrier), radix 4 with a leading radix-2 stage for
+// odd log2 N, twiddles from a 768-entry table of W_1024 in LDS; the inter-step
+// twiddles are sincospi of the exact fraction (n2 k1 < L needs no reduction).
+// No atomics, and a column's arithmetic does not depend on the tile it is in: the
+// result is bit-identical for every workspace size and every C.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+#include <stdio.h>
+#include <algorithm>
+#include "wc_common.h"
+
+namespace {
+
+typedef double d2 __attribute__((ext_vector_type(2)));  // (re, im)
+
+constexpr int64_t kMaxM = 524288;  // L = 2^20 = L1 L2 with L1 = L2 = 1024
+constexpr int kMinLogL = 15;
+constexpr int kThreads = 512;
+constexpr int kPts = 4096;         // points per workgroup
+constexpr int kTwN = 1024;         // sub-FFT twiddle base: T[j] = exp(-2 pi i j / 1024)
+constexpr int kTwLds = 768;        // radix 4 reads j = r k 1024 / (4 P) < 768
+constexpr int kEpt = kPts / kThreads;  // points per thread on load / store
+
+__device__ __forceinline__ d2 cmul(d2 a, d2 w) {
+    return d2{__builtin_fma(a.x, w.x, -a.y * w.y), __builtin_fma(a.x, w.y, a.y * w.x)};
+}
+__device__ __forceinline__ d2 cconj(d2 a) { return d2{a.x, -a.y}; }
+
+// T[j] = exp(-2 pi i j / 1024), j < 1024
+__global__ void hl_twiddle_kernel(d2* T) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= kTwN) return;
+    double s, c;
+    sincospi(2.0 * j / kTwN, &s, &c);
+    T[j] = d2{c, -s};
+}
+
+// w[k] = exp(-i pi k^2 / M): k^2 mod 2 M in integers (k < 2^19), then sincospi
+__global__ void hl_chirp_kernel(int64_t M, d2* w) {
+    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= M) return;
+    const int64_t r = (k * k) % (2 * M);
+    double s, c;
+    sincospi((double)r / (double)M, &s, &c);
+    w[k] = d2{c, -s};
+}
+
+// ---- forward FFT of the workgroup's G sub-FFTs of length N in LDS (item g at z + g (N + 1)) ----
+template <int N>
+__device__ __forceinline__ void r2_stage(d2* z, int tid) {  // first stage, P = 1: no twiddles
+    constexpr int S = N / 2, NP = N + 1, NB = kPts / 2 / kThreads;
+    d2 u[NB][2];
+#pragma unroll
+    for (int j = 0; j < NB; ++j) {
+        const int bf = tid + kThreads * j, g = bf / S, i = bf % S;
+        u[j][0] = z[g * NP + i];
+        u[j][1] = z[g * NP + i + S];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < NB; ++j) {
+        const int bf = tid + kThreads * j, g = bf / S, i = bf % S;
+        z[g * NP + 2 * i] = u[j][0] + u[j][1];
+        z[g * NP + 2 * i + 1] = u[j][0] - u[j][1];
+    }
+    __syncthreads();
+}
+
+// one radix-4 Stockham stage (P = product of the previous radices), as wc_welch.hip's
+template <int N, int P>
+__device__ __forceinline__ void r4_stage(d2* z, const d2* T, int tid) {
+    constexpr int S = N / 4, NP = N + 1, NB = kPts / 4 / kThreads;
+    d2 u[NB][4];
+#pragma unroll
+    for (int j = 0; j < NB; ++j) {
+        const int bf = tid + kThreads * j, g = bf / S, i = bf % S, k = i % P;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) u[j][r] = z[g * NP + i + r * S];
+        if constexpr (P > 1) {
+#pragma unroll
+            for (int r = 1; r < 4; ++r) u[j][r] = cmul(u[j][r], T[r * k * (kTwN / (4 * P))]);
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < NB; ++j) {
+        const int bf = tid + kThreads * j, g = bf / S, i = bf % S, k = i % P;
+        const d2 a = u[j][0] + u[j][2], b = u[j][0] - u[j][2];
+        const d2 c = u[j][1] + u[j][3], d = u[j][1] - u[j][3];
+        d2* o = z + g * NP + (i - k) * 4 + k;
+        o[0] = a + c;
+        o[P] = d2{b.x + d.y, b.y - d.x};  // b - i d
+        o[2 * P] = a - c;
+        o[3 * P] = d2{b.x - d.y, b.y + d.x};  // b + i d
+    }
+    __syncthreads();
+}
+
+template <int N, int P>
+__device__ __forceinline__ void r4_stages(d2* z, const d2* T, int tid) {
+    if constexpr (P < N) {
+        r4_stage<N, P>(z, T, tid);
+        r4_stages<N, P * 4>(z, T, tid);
+    }
+}
+
+// every point of z written and a barrier passed before the call; ends with a barrier
+template <int LOGN>
+__device__ __forceinline__ void fft_lds(d2* z, const d2* T, int tid) {
+    constexpr int N = 1 << LOGN;
+    if constexpr (LOGN & 1) {
+        r2_stage<N>(z, tid);
+        r4_stages<N, 2>(z, T, tid);
+    } else {
+        r4_stages<N, 1>(z, T, tid);
+    }
+}
+
+struct HlArgs {
+    int64_t C, M, c0;  // columns of x, samples, first column of the tile
+    int tc;            // columns of the tile
+    int L, L2;         // FFT length, row length (L1 = L / L2)
+    const double* x;   // [M][C]
+    double* ph;        // [M][C][2]
+    const d2* T;       // W_1024
+    const d2* w;       // chirp [M]
+    d2* Bf;            // chirp spectrum [L], position k1 L2 + k2
+    const d2* src;     // [L][tc]
+    d2* dst;           // [L][tc]
+};
+
+// scipy.signal.hilbert's spectral weights
+__device__ __forceinline__ double hilbert_h(int64_t n, int64_t M) {
+    if (n == 0 || (M % 2 == 0 && n == M / 2)) return 1.0;
+    return n < (M + 1) / 2 ? 2.0 : 0.0;
+}
+
+__device__ __forceinline__ void load_tw(d2* T, const d2* Tg, int tid) {
+    for (int j = tid; j < kTwLds; j += kThreads) T[j] = Tg[j];
+}
+
+enum { kColChirp = 0, kColFirst = 1, kColMid = 2, kColLast = 3 };
+
+// column pass: item q = n2 tc + c, points e = n1 (or k1) at n = e L2 + n2
+template <int LOGN, int MODE>
+__global__ void __launch_bounds__(kThreads) hl_col_kernel(const HlArgs a) {
+    constexpr int N = 1 << LOGN, G = kPts / N, NP = N + 1, ES = kThreads / G;
+    extern __shared__ __attribute__((aligned(16))) d2 hl_smem[];
+    d2* z = hl_smem;
+    d2* T = hl_smem + G * NP;
+    const int tid = threadIdx.x;
+    load_tw(T, a.T, tid);
+    const int g = tid % G, e0 = tid / G;
+    const int64_t q = (int64_t)blockIdx.x * G + g;
+    const int n2 = (int)(q / a.tc), c = (int)(q % a.tc);
+    d2* zg = z + g * NP;
+#pragma unroll
+    for (int j = 0; j < kEpt; ++j) {
+        const int e = e0 + ES * j;
+        const int64_t n = (int64_t)e * a.L2 + n2;
+        d2 v = d2{0.0, 0.0};
+        if constexpr (MODE == kColChirp) {  // conj(w) at n = m mod L, |m| < M
+            const int64_t m = n < a.M ? n : (n > a.L - a.M ? a.L - n : -1);
+            if (m >= 0) v = cconj(a.w[m]);
+        } else if constexpr (MODE == kColFirst) {
+            if (n < a.M) v = a.x[n * a.C + a.c0 + c] * a.w[n];
+        } else {  // inverse sub-FFT as conj(FFT(conj(.)))
+            v = cconj(a.src[n * a.tc + c]);
+        }
+        zg[e] = v;
+    }
+    __syncthreads();
+    if constexpr (MODE == kColMid || MODE == kColLast) {
+        fft_lds<LOGN>(z, T, tid);  // F = conj(c) L, c = the circular convolution
+        const double sc = 1.0 / (double)a.L;
+#pragma unroll
+        for (int j = 0; j < kEpt; ++j) {
+            const int e = e0 + ES * j;
+            const int64_t n = (int64_t)e * a.L2 + n2;
+            const d2 F = zg[e];
+            if constexpr (MODE == kColMid) {
+                // X = w c; the next DFT's input conj(X h) w = conj(c) h (|w| = 1)
+                zg[e] = n < a.M ? F * (sc * hilbert_h(n, a.M)) : d2{0.0, 0.0};
+            } else if (n < a.M) {
+                // analytic signal = conj(w c') / M, c' = conj(F) / L: phase of conj(w) F
+                const d2 s = cmul(F, cconj(a.w[n])) * sc;
+                const double r = sqrt(s.x * s.x + s.y * s.y);
+                d2* o = reinterpret_cast<d2*>(a.ph) + n * a.C + a.c0 + c;
+                *o = r > 0 ? d2{s.x / r, s.y / r} : d2{1.0, 0.0};  // numpy: angle(0) = 0
+            }
+        }
+        if constexpr (MODE == kColLast) return;
+        __syncthreads();
+    }
+    fft_lds<LOGN>(z, T, tid);
+#pragma unroll
+    for (int j = 0; j < kEpt; ++j) {
+        const int e = e0 + ES * j;
+        const int64_t n = (int64_t)e * a.L2 + n2;
+        double s, co;
+        sincospi(2.0 * (double)((int64_t)n2 * e) / (double)a.L, &s, &co);  // W_L^(n2 k1), n2 k1 < L
+        a.dst[n * a.tc + c] = cmul(zg[e], d2{co, -s});
+    }
+}
+
+// row pass: item q = k1 tc + c, points e = n2 (or k2) at k1 L2 + e
+template <int LOGN, bool CONV>
+__global__ void __launch_bounds__(kThreads) hl_row_kernel(const HlArgs a) {
+    constexpr int N = 1 << LOGN, G = kPts / N, NP = N + 1, ES = kThreads / G;
+    extern __shared__ __attribute__((aligned(16))) d2 hl_smem[];
+    d2* z = hl_smem;
+    d2* T = hl_smem + G * NP;
+    const int tid = threadIdx.x;
+    load_tw(T, a.T, tid);
+    const int g = tid % G, e0 = tid / G;
+    const int64_t q = (int64_t)blockIdx.x * G + g;
+    const int k1 = (int)(q / a.tc), c = (int)(q % a.tc);
+    d2* zg = z + g * NP;
+    const int64_t row = (int64_t)k1 * N;
+#pragma unroll
+    for (int j = 0; j < kEpt; ++j) {
+        const int e = e0 + ES * j;
+        zg[e] = a.src[(row + e) * a.tc + c];
+    }
+    __syncthreads();
+    fft_lds<LOGN>(z, T, tid);
+    if constexpr (!CONV) {  // the chirp spectrum (tc = 1)
+#pragma unroll
+        for (int j = 0; j < kEpt; ++j) {
+            const int e = e0 + ES * j;
+            a.Bf[row + e] = zg[e];
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < kEpt; ++j) {
+            const int e = e0 + ES * j;
+            zg[e] = cconj(cmul(zg[e], a.Bf[row + e]));
+        }
+        __syncthreads();
+        fft_lds<LOGN>(z, T, tid);
+#pragma unroll
+        for (int j = 0; j < kEpt; ++j) {
+            const int e = e0 + ES * j;
+            double s, co;
+            sincospi(2.0 * (double)((int64_t)k1 * e) / (double)a.L, &s, &co);  // conj(W_L^(k1 n2))
+            a.dst[(row + e) * a.tc + c] = cconj(cmul(zg[e], d2{co, -s}));
+        }
+    }
+}
+
+template <int N> constexpr size_t hl_lds_bytes() { return ((size_t)kPts + kPts / N + kTwLds) * sizeof(d2); }
+
+template <int LOGN, int MODE>
+hipError_t launch_col(const HlArgs& a, int64_t items, hipStream_t st) {
+    constexpr int N = 1 << LOGN;
+    auto kern = hl_col_kernel<LOGN, MODE>;
+    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       (int)hl_lds_bytes<N>());
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kern, dim3((unsigned)(items / (kPts / N))), dim3(kThreads), hl_lds_bytes<N>(), st, a);
+    return hipSuccess;
+}
+template <int LOGN, bool CONV>
+hipError_t launch_row(const HlArgs& a, int64_t items, hipStream_t st) {
+    constexpr int N = 1 << LOGN;
+    auto kern = hl_row_kernel<LOGN, CONV>;
+    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       (int)hl_lds_bytes<N>());
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kern, dim3((unsigned)(items / (kPts / N))), dim3(kThreads), hl_lds_bytes<N>(), st, a);
+    return hipSuccess;
+}
+
+template <int MODE>
+hipError_t col_pass(int log1, const HlArgs& a, hipStream_t st) {
+    const int64_t items = (int64_t)a.L2 * a.tc;  // a multiple of G: L2 >= 128 >= G
+    switch (log1) {
+        case 8: return launch_col<8, MODE>(a, items, st);
+        case 9: return launch_col<9, MODE>(a, items, st);
+        default: return launch_col<10, MODE>(a, items, st);
+    }
+}
+template <bool CONV>
+hipError_t row_pass(int log2, const HlArgs& a, hipStream_t st) {
+    const int64_t items = (int64_t)(a.L / a.L2) * a.tc;
+    switch (log2) {
+        case 7: return launch_row<7, CONV>(a, items, st);
+        case 8: return launch_row<8, CONV>(a, items, st);
+        case 9: return launch_row<9, CONV>(a, items, st);
+        default: return launch_row<10, CONV>(a, items, st);
+    }
+}
+
+int hl_log_len(int64_t M) {  // log2 L, L = max(2^15, nextpow2(2 M - 1))
+    int l = kMinLogL;
+    while (((int64_t)1 << l) < 2 * M - 1) ++l;
+    return l;
+}
+// workspace: W_1024 | chirp w [M] (padded to a 256-B multiple) | chirp spectrum [L] | 2 x [L][tc]
+size_t hl_chirp_elems(int64_t M) { return (size_t)((M + 15) / 16 * 16); }
+size_t hl_table_bytes(int64_t M, int64_t L) { return ((size_t)kTwN + hl_chirp_elems(M) + (size_t)L) * sizeof(d2); }
+
+}  // namespace
+
+size_t wc_hilbert_long_workspace_size(int64_t C, int64_t M) {
+    if (C <= 0 || M < 2 || M > kMaxM) return 0;
+    const int64_t L = (int64_t)1 << hl_log_len(M);
+    return hl_table_bytes(M, L) + 2 * (size_t)L * sizeof(d2);
+}
+
+int wc_hilbert_phase_long(int64_t C, int64_t M, const double* x, double* phasor, void* workspace, size_t ws_bytes,
+                          void* stream) {
+    wc_clear_err();
+    if (C <= 0 || M < 2 || !x || !phasor) return wc_set_err(WC_EINVAL, "wc_hilbert_phase_long: bad arguments");
+    if (M > kMaxM)
+        return wc_set_err(WC_EUNSUPPORTED, "wc_hilbert_phase_long: M > 524288 (the FFT length 2^20 = 1024 x 1024)");
+    const int logL = hl_log_len(M), log1 = (logL + 1) / 2, log2 = logL / 2;  // 8..10, 7..10
+    const int64_t L = (int64_t)1 << logL;
+    const size_t tab = hl_table_bytes(M, L), per_col = 2 * (size_t)L * sizeof(d2);
+    if (!workspace || ws_bytes < tab + per_col) {
+        char msg[160];
+        snprintf(msg, sizeof msg, "wc_hilbert_phase_long: workspace < %zu bytes (wc_hilbert_long_workspace_size)",
+                 tab + per_col);
+        return wc_set_err(WC_EWORKSPACE, msg);
+    }
+    if (((uintptr_t)workspace & 15) || ((uintptr_t)phasor & 15))
+        return wc_set_err(WC_EINVAL, "wc_hilbert_phase_long: workspace and phasor must be 16-byte aligned");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    d2* T = static_cast<d2*>(workspace);
+    d2* w = T + kTwN;
+    d2* Bf = w + hl_chirp_elems(M);
+    d2* buf0 = Bf + L;
+    const int64_t tcmax = (int64_t)std::min<size_t>((ws_bytes - tab) / per_col, (size_t)std::min<int64_t>(C, 1 << 20));
+
+    hipLaunchKernelGGL(hl_twiddle_kernel, dim3(kTwN / 256), dim3(256), 0, st, T);
+    hipLaunchKernelGGL(hl_chirp_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, st, M, w);
+    HlArgs a{C, M, 0, 1, (int)L, 1 << log2, x, phasor, T, w, Bf, nullptr, buf0};
+    hipError_t e = col_pass<kColChirp>(log1, a, st);
+    a.src = buf0;
+    if (e == hipSuccess) e = row_pass<false>(log2, a, st);
+    for (int64_t c0 = 0; c0 < C && e == hipSuccess; c0 += tcmax) {
+        a.c0 = c0;
+        a.tc = (int)std::min<int64_t>(tcmax, C - c0);
+        d2* buf1 = buf0 + (size_t)L * a.tc;
+        a.src = nullptr, a.dst = buf0;
+        e = col_pass<kColFirst>(log1, a, st);
+        a.src = buf0, a.dst = buf1;
+        if (e == hipSuccess) e = row_pass<true>(log2, a, st);
+        a.src = buf1, a.dst = buf0;
+        if (e == hipSuccess) e = col_pass<kColMid>(log1, a, st);
+        a.src = buf0, a.dst = buf1;
+        if (e == hipSuccess) e = row_pass<true>(log2, a, st);
+        a.src = buf1, a.dst = nullptr;
+        if (e == hipSuccess) e = col_pass<kColLast>(log1, a, st);
+    }
+    if (e != hipSuccess) {
+        snprintf(wc_errbuf(), 512, "wc_hilbert_phase_long: %s", hipGetErrorString(e));
+        return WC_EHIP;
+    }
+    return wc_hip_check("wc_hilbert_phase_long");
+}

@@ -901,7 +901,7 @@ __global__ void __launch_bounds__(kFcThreads) fc_metrics_kernel(const FcArgs a) 
     double sync = 0, meta = 0;
     if (a.ph) {
         double r1 = 0, r2 = 0;
-        for (int t = tid; t < M; t += blockDim.x) {
+        auto order = [&](int t) {
             double cr = 0, ci = 0;
             const double* p = a.ph + ((int64_t)t * C + (int64_t)b * N) * 2;
             for (int n = 0; n < N; ++n) {
@@ -910,12 +910,21 @@ __global__ void __launch_bounds__(kFcThreads) fc_metrics_kernel(const FcArgs a) 
             }
             cr /= N;
             ci /= N;
-            const double R = sqrt(cr * cr + ci * ci);
+            return sqrt(cr * cr + ci * ci);
+        };
+        // R(t) is kept in emp (free now) while it fits, N * N samples; a longer series
+        // (bold_downsamp < 1000) forms it again in the second pass: the same values
+        const bool keep = M <= NN;
+        for (int t = tid; t < M; t += blockDim.x) {
+            const double R = order(t);
             r1 += R;
-            emp[t] = R;  // emp is free now
+            if (keep) emp[t] = R;
         }
         sync = block_sum(r1, red) / M;
-        for (int t = tid; t < M; t += blockDim.x) r2 += (emp[t] - sync) * (emp[t] - sync);
+        for (int t = tid; t < M; t += blockDim.x) {
+            const double R = keep ? emp[t] : order(t);
+            r2 += (R - sync) * (R - sync);
+        }
         meta = sqrt(block_sum(r2, red) / M);
     }
     if (tid == 0) {
@@ -1158,6 +1167,8 @@ int wc_hilbert_phase(int64_t C, int M, const double* x, double* phasor, void* wo
                      void* stream) {
     wc_clear_err();
     if (C <= 0 || M <= 1 || !x || !phasor) return wc_set_err(WC_EINVAL, "wc_hilbert_phase: bad arguments");
+    if ((size_t)M * sizeof(double) > 65536)  // q[0..M) in a 64 KB dynamic-LDS launch
+        return wc_set_err(WC_EUNSUPPORTED, "wc_hilbert_phase: M > 8192 (use wc_hilbert_phase_long)");
     if (!workspace || ws_bytes < (size_t)M * sizeof(double))
         return wc_set_err(WC_EWORKSPACE, "wc_hilbert_phase: workspace < M doubles");
     hipStream_t st = static_cast<hipStream_t>(stream);

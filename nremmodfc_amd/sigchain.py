@@ -77,12 +77,43 @@ class BoldStream:
 
 
 def hilbert_phase(x):
-    """Unit phasors of hilbert(x, axis=0) for x [M][C] fp64 -> [M][C][2]."""
+    """Unit phasors of hilbert(x, axis=0) for x [M][C] fp64 -> [M][C][2].
+
+    M <= 8192 (HILBERT_DIRECT_MAX_M) takes wc_hilbert_phase, the direct O(M^2)
+    convolution; longer series, up to M = 524288, take wc_hilbert_phase_long
+    (Bluestein over a power-of-two FFT, O(M log M)) with a workspace for as many
+    columns in flight as HILBERT_LONG_WS_CAP allows.  M > 524288 raises."""
     M, C = x.shape
     ph = torch.empty((M, C, 2), dtype=torch.float64, device=x.device)
-    ws = torch.empty(M, dtype=torch.float64, device=x.device)
-    _lib.check(_lib.lib().wc_hilbert_phase(C, M, _lib.ptr(x.contiguous()), _lib.ptr(ph), _lib.ptr(ws),
-                                           ws.numel() * 8, _lib.stream_handle()), "wc_hilbert_phase")
+    if M <= HILBERT_DIRECT_MAX_M:
+        ws = torch.empty(M, dtype=torch.float64, device=x.device)
+        _lib.check(_lib.lib().wc_hilbert_phase(C, M, _lib.ptr(x.contiguous()), _lib.ptr(ph), _lib.ptr(ws),
+                                               ws.numel() * 8, _lib.stream_handle()), "wc_hilbert_phase")
+        return ph
+    return hilbert_phase_long(x, ph)
+
+
+HILBERT_DIRECT_MAX_M = 8192       # wc_hilbert_phase: M * 8 bytes of LDS in a 64 KB launch
+HILBERT_LONG_WS_CAP = 1 << 30     # wc_hilbert_phase_long: workspace ceiling (column tiles beyond it)
+
+
+def hilbert_phase_long(x, out=None, ws_bytes=None):
+    """wc_hilbert_phase_long for x [M][C] fp64, any 2 <= M <= 524288 -> [M][C][2].
+
+    ws_bytes: workspace size (default: what all C columns want, at most
+    HILBERT_LONG_WS_CAP, never below the minimum); the result does not depend on it."""
+    L = _lib.lib()
+    M, C = x.shape
+    need = L.wc_hilbert_long_workspace_size(C, M)
+    if need == 0:
+        raise _lib.WCSDEError(f"hilbert_phase: M = {M} outside 2 .. 524288 (or no columns)")
+    if ws_bytes is None:
+        fft_len = max(1 << 15, 1 << (2 * M - 2).bit_length())  # max(2^15, nextpow2(2 M - 1))
+        ws_bytes = max(need, min(need + (C - 1) * 32 * fft_len, HILBERT_LONG_WS_CAP))
+    ph = torch.empty((M, C, 2), dtype=torch.float64, device=x.device) if out is None else out
+    ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.float64, device=x.device)
+    _lib.check(L.wc_hilbert_phase_long(C, M, _lib.ptr(x.contiguous()), _lib.ptr(ph), _lib.ptr(ws), ws_bytes,
+                                       _lib.stream_handle()), "wc_hilbert_phase_long")
     return ph
 
 

@@ -1,7 +1,7 @@
 """Drop-in for the FC/observable part of utils.py (utils.py:18-50).
 
 get_all_metrics and kuramoto run in libwcsde.so (wc_fc_metrics,
-wc_hilbert_phase + wc_kuramoto); the small array helpers the reference defines
+wc_hilbert_phase / wc_hilbert_phase_long + wc_kuramoto); the small array helpers the reference defines
 next to them (flat_FC, new_metric, cohen_d) are kept as host numpy one-liners
 for callers that import them.  Plotting/analysis helpers of utils.py
 (sub_weight, cortex_mat, RSN_profile_FC, find_extreme, xy2plotcor,
@@ -37,7 +37,11 @@ def new_metric(flat1, flat2):
 
 def kuramoto(sign):
     """utils.py:34-40: (sync, meta) of the Kuramoto order parameter of sign (T x N)
-    from the phases of its analytic signal (hilbert along axis 0)."""
+    from the phases of its analytic signal (hilbert along axis 0).
+
+    2 <= T <= 524288: series of up to 8192 samples take the direct convolution
+    (wc_hilbert_phase), longer ones the FFT path (wc_hilbert_phase_long), e.g.
+    cortex_run.py's 29,800-sample BOLD and 300,000-sample E_t."""
     x = torch.as_tensor(np.ascontiguousarray(sign, dtype=np.float64)).to(device)
     if x.ndim != 2:
         raise ValueError("sign must be (time, nodes)")
