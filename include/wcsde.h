@@ -234,9 +234,10 @@ int wc_hopf_integrate(const wc_hopf_params* p, int B, int N, const double* M, co
 /* scipy.signal.filtfilt(b, a, x, axis=0) of every column of x [T][C] fp64 ->
  * y [T][C] (y must not alias x): odd extension of padlen = 3 (order + 1),
  * lfilter_zi initial conditions zi[order] (host, from the caller), DF2T in
- * scipy's association order.  order in {2, 4, 6, 8}; b, a, zi are HOST
- * arrays of order + 1, order + 1 and order doubles, a[0] == 1.
- * (optimize_SC_Hopf.py:63-66; also any simBOLD-style band-pass.) */
+ * scipy's association order.  1 <= order <= 8 (utils.envelope's low-pass is
+ * order 3); T must exceed padlen; b, a, zi are HOST arrays of order + 1,
+ * order + 1 and order doubles, a[0] == 1.
+ * (optimize_SC_Hopf.py:63-66, utils.py:145-154; also any simBOLD-style band-pass.) */
 int wc_filtfilt(int order, const double* b, const double* a, const double* zi, int64_t T, int64_t C,
                 const double* x, double* y, void* stream);
 
@@ -260,6 +261,20 @@ int wc_hilbert_phase(int64_t C, int M, const double* x, double* phasor, void* wo
 size_t wc_hilbert_long_workspace_size(int64_t C, int64_t M);
 int wc_hilbert_phase_long(int64_t C, int64_t M, const double* x, double* phasor, void* workspace,
                           size_t ws_bytes, void* stream);
+
+/* |scipy.signal.hilbert(x, axis=0)| of every column of x [M][C] fp64 -> env
+ * [M][C] fp64 (utils.envelope, utils.py:149), 2 <= M <= 524288.  method: 1 =
+ * the direct convolution of wc_hilbert_phase (M <= 8192, else WC_EUNSUPPORTED;
+ * workspace M doubles), 2 = the Bluestein pipeline of wc_hilbert_phase_long
+ * (workspace as wc_hilbert_long_workspace_size: the returned minimum holds one
+ * column, every further 32 L bytes one more in flight, 16-byte aligned, result
+ * bit-identical for every workspace size and every C), 0 = whichever is
+ * faster: direct below M = 2048, long from there on.  env must not alias x.
+ * The size function returns 0 where the call would not return WC_OK or
+ * WC_EWORKSPACE. */
+size_t wc_hilbert_envelope_workspace_size(int64_t C, int64_t M, int method);
+int wc_hilbert_envelope(int64_t C, int64_t M, const double* x, double* env, int method,
+                        void* workspace, size_t ws_bytes, void* stream);
 
 /* Per simulation b of bold [M][B][N] (the filtered, decimated BOLD; or, with
  * bold == NULL, of the given fc_in [B][N][N]):

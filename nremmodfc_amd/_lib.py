@@ -61,6 +61,8 @@ _SIGNATURES = {
     "wc_hilbert_phase": (c_int, [c_i64, c_int, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "wc_hilbert_long_workspace_size": (c_sz, [c_i64, c_i64]),
     "wc_hilbert_phase_long": (c_int, [c_i64, c_i64, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "wc_hilbert_envelope_workspace_size": (c_sz, [c_i64, c_i64, c_int]),
+    "wc_hilbert_envelope": (c_int, [c_i64, c_i64, c_vp, c_vp, c_int, c_vp, c_sz, c_vp]),
     "wc_fc_metrics_workspace_size": (c_sz, [c_int, c_int, c_int, c_int, c_int]),
     "wc_fc_metrics": (c_int, [c_int, c_int, c_int, c_vp, c_vp, c_vp, c_int, c_dbl, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz,
                               c_vp]),

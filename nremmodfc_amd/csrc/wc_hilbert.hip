@@ -1,5 +1,5 @@
-// wc_hilbert.hip -- Hilbert phases of long series (gfx950): utils.kuramoto's
-// scipy.signal.hilbert(x, axis=0) for 2 <= M <= 524,288 samples per column.
+// wc_hilbert.hip -- Hilbert phases and envelopes of long series (gfx950): utils.kuramoto's
+// and utils.envelope's scipy.signal.hilbert(x, axis=0) for 2 <= M <= 524,288 samples per column.
 //
 // The analytic signal needs the exact length-M DFT (scipy pads nothing), and M is
 // arbitrary (cortex_run.py's BOLD has 29,800 = 2^3 5^2 149 samples), so both DFTs
@@ -21,7 +21,7 @@
 //   2. row  FFT_L2, times the chirp spectrum, IFFT_L2, conjugate twiddle
 //   3. col  IFFT_L1 -> conj(c) h / L (= conj(X h) w: the second DFT's input) -> FFT_L1, twiddle
 //   4. row  as 2
-//   5. col  IFFT_L1 -> conj(w) . = the analytic signal (up to a positive scale) -> unit phasor
+//   5. col  IFFT_L1 -> conj(w) . = M times the analytic signal -> unit phasor, or modulus / M
 // Work buffers are [L][tc] complex for a tile of tc columns (the columns of one
 // point are contiguous), two of them, each pass reading one and writing the other.
 // A workgroup (512 threads) owns 4096 points in LDS: G = 4096 / N sub-FFTs of length
@@ -151,7 +151,7 @@ struct HlArgs {
     int tc;            // columns of the tile
     int L, L2;         // FFT length, row length (L1 = L / L2)
     const double* x;   // [M][C]
-    double* ph;        // [M][C][2]
+    double* ph;        // [M][C][2] unit phasors, or [M][C] moduli (kColLastEnv)
     const d2* T;       // W_1024
     const d2* w;       // chirp [M]
     d2* Bf;            // chirp spectrum [L], position k1 L2 + k2
@@ -169,7 +169,7 @@ __device__ __forceinline__ void load_tw(d2* T, const d2* Tg, int tid) {
     for (int j = tid; j < kTwLds; j += kThreads) T[j] = Tg[j];
 }
 
-enum { kColChirp = 0, kColFirst = 1, kColMid = 2, kColLast = 3 };
+enum { kColChirp = 0, kColFirst = 1, kColMid = 2, kColLast = 3, kColLastEnv = 4 };
 
 // column pass: item q = n2 tc + c, points e = n1 (or k1) at n = e L2 + n2
 template <int LOGN, int MODE>
@@ -200,7 +200,8 @@ __global__ void __launch_bounds__(kThreads) hl_col_kernel(const HlArgs a) {
         zg[e] = v;
     }
     __syncthreads();
-    if constexpr (MODE == kColMid || MODE == kColLast) {
+    constexpr bool kLast = MODE == kColLast || MODE == kColLastEnv;
+    if constexpr (MODE == kColMid || kLast) {
         fft_lds<LOGN>(z, T, tid);  // F = conj(c) L, c = the circular convolution
         const double sc = 1.0 / (double)a.L;
 #pragma unroll
@@ -214,12 +215,17 @@ __global__ void __launch_bounds__(kThreads) hl_col_kernel(const HlArgs a) {
             } else if (n < a.M) {
                 // analytic signal = conj(w c') / M, c' = conj(F) / L: phase of conj(w) F
                 const d2 s = cmul(F, cconj(a.w[n])) * sc;
+                // (sc is the second convolution's 1 / L; the inverse DFT's 1 / M is still owed)
                 const double r = sqrt(s.x * s.x + s.y * s.y);
-                d2* o = reinterpret_cast<d2*>(a.ph) + n * a.C + a.c0 + c;
-                *o = r > 0 ? d2{s.x / r, s.y / r} : d2{1.0, 0.0};  // numpy: angle(0) = 0
+                if constexpr (MODE == kColLastEnv) {
+                    a.ph[n * a.C + a.c0 + c] = r / (double)a.M;
+                } else {
+                    d2* o = reinterpret_cast<d2*>(a.ph) + n * a.C + a.c0 + c;
+                    *o = r > 0 ? d2{s.x / r, s.y / r} : d2{1.0, 0.0};  // numpy: angle(0) = 0
+                }
             }
         }
-        if constexpr (MODE == kColLast) return;
+        if constexpr (kLast) return;
         __syncthreads();
     }
     fft_lds<LOGN>(z, T, tid);
@@ -338,23 +344,23 @@ size_t wc_hilbert_long_workspace_size(int64_t C, int64_t M) {
     return hl_table_bytes(M, L) + 2 * (size_t)L * sizeof(d2);
 }
 
-int wc_hilbert_phase_long(int64_t C, int64_t M, const double* x, double* phasor, void* workspace, size_t ws_bytes,
-                          void* stream) {
-    wc_clear_err();
-    if (C <= 0 || M < 2 || !x || !phasor) return wc_set_err(WC_EINVAL, "wc_hilbert_phase_long: bad arguments");
-    if (M > kMaxM)
-        return wc_set_err(WC_EUNSUPPORTED, "wc_hilbert_phase_long: M > 524288 (the FFT length 2^20 = 1024 x 1024)");
+// the five passes over column tiles, for both outputs: out is phasor [M][C][2] (16-byte aligned) or,
+// with envelope, env [M][C]; `who` names the entry point in messages
+static int hl_run(const char* who, bool envelope, int64_t C, int64_t M, const double* x, double* out, void* workspace,
+                  size_t ws_bytes, void* stream) {
+    char msg[200];
     const int logL = hl_log_len(M), log1 = (logL + 1) / 2, log2 = logL / 2;  // 8..10, 7..10
     const int64_t L = (int64_t)1 << logL;
     const size_t tab = hl_table_bytes(M, L), per_col = 2 * (size_t)L * sizeof(d2);
     if (!workspace || ws_bytes < tab + per_col) {
-        char msg[160];
-        snprintf(msg, sizeof msg, "wc_hilbert_phase_long: workspace < %zu bytes (wc_hilbert_long_workspace_size)",
-                 tab + per_col);
+        snprintf(msg, sizeof msg, "%s: workspace < %zu bytes (%s)", who, tab + per_col,
+                 envelope ? "wc_hilbert_envelope_workspace_size" : "wc_hilbert_long_workspace_size");
         return wc_set_err(WC_EWORKSPACE, msg);
     }
-    if (((uintptr_t)workspace & 15) || ((uintptr_t)phasor & 15))
-        return wc_set_err(WC_EINVAL, "wc_hilbert_phase_long: workspace and phasor must be 16-byte aligned");
+    if (((uintptr_t)workspace & 15) || ((uintptr_t)out & (envelope ? 7 : 15))) {  // d2 stores; env: doubles
+        snprintf(msg, sizeof msg, "%s: workspace%s must be 16-byte aligned", who, envelope ? "" : " and phasor");
+        return wc_set_err(WC_EINVAL, msg);
+    }
     hipStream_t st = static_cast<hipStream_t>(stream);
     d2* T = static_cast<d2*>(workspace);
     d2* w = T + kTwN;
@@ -364,7 +370,7 @@ int wc_hilbert_phase_long(int64_t C, int64_t M, const double* x, double* phasor,
 
     hipLaunchKernelGGL(hl_twiddle_kernel, dim3(kTwN / 256), dim3(256), 0, st, T);
     hipLaunchKernelGGL(hl_chirp_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, st, M, w);
-    HlArgs a{C, M, 0, 1, (int)L, 1 << log2, x, phasor, T, w, Bf, nullptr, buf0};
+    HlArgs a{C, M, 0, 1, (int)L, 1 << log2, x, out, T, w, Bf, nullptr, buf0};
     hipError_t e = col_pass<kColChirp>(log1, a, st);
     a.src = buf0;
     if (e == hipSuccess) e = row_pass<false>(log2, a, st);
@@ -381,11 +387,26 @@ int wc_hilbert_phase_long(int64_t C, int64_t M, const double* x, double* phasor,
         a.src = buf0, a.dst = buf1;
         if (e == hipSuccess) e = row_pass<true>(log2, a, st);
         a.src = buf1, a.dst = nullptr;
-        if (e == hipSuccess) e = col_pass<kColLast>(log1, a, st);
+        if (e == hipSuccess) e = envelope ? col_pass<kColLastEnv>(log1, a, st) : col_pass<kColLast>(log1, a, st);
     }
     if (e != hipSuccess) {
-        snprintf(wc_errbuf(), 512, "wc_hilbert_phase_long: %s", hipGetErrorString(e));
+        snprintf(wc_errbuf(), 512, "%s: %s", who, hipGetErrorString(e));
         return WC_EHIP;
     }
-    return wc_hip_check("wc_hilbert_phase_long");
+    return wc_hip_check(who);
+}
+
+int wc_hilbert_phase_long(int64_t C, int64_t M, const double* x, double* phasor, void* workspace, size_t ws_bytes,
+                          void* stream) {
+    wc_clear_err();
+    if (C <= 0 || M < 2 || !x || !phasor) return wc_set_err(WC_EINVAL, "wc_hilbert_phase_long: bad arguments");
+    if (M > kMaxM)
+        return wc_set_err(WC_EUNSUPPORTED, "wc_hilbert_phase_long: M > 524288 (the FFT length 2^20 = 1024 x 1024)");
+    return hl_run("wc_hilbert_phase_long", false, C, M, x, phasor, workspace, ws_bytes, stream);
+}
+
+// wc_hilbert_envelope's long method (the entry point, its validation and the dispatch: wc_signal.hip)
+int wc_hilbert_envelope_long(int64_t C, int64_t M, const double* x, double* env, void* workspace, size_t ws_bytes,
+                             void* stream) {
+    return hl_run("wc_hilbert_envelope", true, C, M, x, env, workspace, ws_bytes, stream);
 }

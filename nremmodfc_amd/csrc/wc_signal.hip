@@ -36,6 +36,9 @@ size_t wc_large_fc_metrics_workspace_size(int B, int N, int K, int own_fc);
 int wc_large_fc_metrics(int B, int N, int M, const double* bold, const double* fc_in, const double* empfc, int K,
                         double data_range, const double* kur, double* fc_out, double* metrics, double* extra,
                         void* workspace, size_t ws_bytes, hipStream_t st);
+// wc_hilbert_envelope's long method: wc_hilbert.hip
+int wc_hilbert_envelope_long(int64_t C, int64_t M, const double* x, double* env, void* workspace, size_t ws_bytes,
+                             void* stream);
 
 namespace {
 
@@ -583,9 +586,11 @@ __global__ void bold_finish_kernel(const FinishArgs f, const double* __restrict_
 // ---------------- Hilbert phases (utils.kuramoto's hilbert, axis 0) ----------------
 // imag(hilbert(x))[t] = sum_tau x[tau] q[(t - tau) mod M],  q[d] = (2/M) sum_{k=1}^{K} sin(2 pi k d / M)
 // (K = M/2 - 1 for even M, (M-1)/2 for odd): the analytic signal's real part is
-// x itself.  Output: unit phasor (cos, sin) of angle(x + i H) per [t][c].
+// x itself.  Output: unit phasor (cos, sin) of angle(x + i H) per [t][c], or (ENV) the
+// modulus sqrt(x^2 + H^2) per [t][c].
 constexpr int kHilNodes = 8;    // columns per workgroup
 constexpr int kHilT = 32;       // time slices per column
+template <bool ENV>
 __global__ void __launch_bounds__(256) hilbert_phase_kernel(int64_t C, int M, const double* __restrict__ x,
                                                             const double* __restrict__ qk,
                                                             double* __restrict__ ph) {
@@ -616,8 +621,12 @@ __global__ void __launch_bounds__(256) hilbert_phase_kernel(int64_t C, int M, co
             if (t < te) {
                 const double re = x[(int64_t)t * C + c];
                 const double r = sqrt(re * re + acc[k] * acc[k]);
-                ph[((int64_t)t * C + c) * 2] = r > 0 ? re / r : 1.0;  // numpy: angle(0) = 0
-                ph[((int64_t)t * C + c) * 2 + 1] = r > 0 ? acc[k] / r : 0.0;
+                if constexpr (ENV) {
+                    ph[(int64_t)t * C + c] = r;
+                } else {
+                    ph[((int64_t)t * C + c) * 2] = r > 0 ? re / r : 1.0;  // numpy: angle(0) = 0
+                    ph[((int64_t)t * C + c) * 2 + 1] = r > 0 ? acc[k] / r : 0.0;
+                }
             }
         }
     }
@@ -1174,9 +1183,47 @@ int wc_hilbert_phase(int64_t C, int M, const double* x, double* phasor, void* wo
     hipStream_t st = static_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(hilbert_kernel_q, dim3((M + 255) / 256), dim3(256), 0, st, M, static_cast<double*>(workspace));
     const unsigned blocks = (unsigned)((C + kHilNodes - 1) / kHilNodes);
-    hipLaunchKernelGGL(hilbert_phase_kernel, dim3(blocks), dim3(kHilNodes * kHilT), M * sizeof(double), st, C, M, x,
-                       static_cast<const double*>(workspace), phasor);
+    hipLaunchKernelGGL(hilbert_phase_kernel<false>, dim3(blocks), dim3(kHilNodes * kHilT), M * sizeof(double), st, C,
+                       M, x, static_cast<const double*>(workspace), phasor);
     return wc_hip_check("wc_hilbert_phase");
+}
+
+// method 0 takes the direct convolution below this M and the Bluestein FFT from it on (by speed,
+// measured at C = 5760: docs/CHANGELOG.md); the direct kernel's own range ends at kHilDirectMaxM
+constexpr int64_t kHilEnvAutoLongM = 2048;
+constexpr int64_t kHilDirectMaxM = 8192;  // q[0..M) in a 64 KB dynamic-LDS launch
+constexpr int64_t kHilLongMaxM = 524288;
+
+static bool hil_env_long(int64_t M, int method) { return method == 2 || (method == 0 && M >= kHilEnvAutoLongM); }
+
+size_t wc_hilbert_envelope_workspace_size(int64_t C, int64_t M, int method) {
+    if (C <= 0 || M < 2 || M > kHilLongMaxM || method < 0 || method > 2 || (method == 1 && M > kHilDirectMaxM))
+        return 0;
+    return hil_env_long(M, method) ? wc_hilbert_long_workspace_size(C, M) : (size_t)M * sizeof(double);
+}
+
+int wc_hilbert_envelope(int64_t C, int64_t M, const double* x, double* env, int method, void* workspace,
+                        size_t ws_bytes, void* stream) {
+    wc_clear_err();
+    if (C <= 0 || M < 2 || !x || !env || x == env || method < 0 || method > 2)
+        return wc_set_err(WC_EINVAL, "wc_hilbert_envelope: NULL pointer, C <= 0, M < 2, env aliasing x or method not 0..2");
+    if (((uintptr_t)x & 7) || ((uintptr_t)env & 7))
+        return wc_set_err(WC_EINVAL, "wc_hilbert_envelope: x and env must be 8-byte aligned");
+    if (M > kHilLongMaxM)
+        return wc_set_err(WC_EUNSUPPORTED, "wc_hilbert_envelope: M > 524288 (the FFT length 2^20 = 1024 x 1024)");
+    if (method == 1 && M > kHilDirectMaxM)
+        return wc_set_err(WC_EUNSUPPORTED, "wc_hilbert_envelope: method 1 (direct) takes M <= 8192");
+    if (hil_env_long(M, method)) return wc_hilbert_envelope_long(C, M, x, env, workspace, ws_bytes, stream);
+    if (!workspace || ws_bytes < (size_t)M * sizeof(double))
+        return wc_set_err(WC_EWORKSPACE, "wc_hilbert_envelope: workspace < M doubles (wc_hilbert_envelope_workspace_size)");
+    if ((uintptr_t)workspace & 7) return wc_set_err(WC_EINVAL, "wc_hilbert_envelope: workspace must be 8-byte aligned");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(hilbert_kernel_q, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, st, (int)M,
+                       static_cast<double*>(workspace));
+    const unsigned blocks = (unsigned)((C + kHilNodes - 1) / kHilNodes);
+    hipLaunchKernelGGL(hilbert_phase_kernel<true>, dim3(blocks), dim3(kHilNodes * kHilT), (size_t)M * sizeof(double), st,
+                       C, (int)M, x, static_cast<const double*>(workspace), env);
+    return wc_hip_check("wc_hilbert_envelope");
 }
 
 int wc_kuramoto(int B, int N, int M, const double* phasor, double* out, void* stream) {

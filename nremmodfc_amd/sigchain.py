@@ -1,14 +1,16 @@
 """Device-side signal chain: BOLD + band-pass filtfilt + decimation, FC and
-goodness of fit, Kuramoto, Welch peak -- thin wrappers over libwcsde.so.
+goodness of fit, Kuramoto, Welch peak, band-limited amplitude envelopes -- thin
+wrappers over libwcsde.so.
 
 References: simBOLD netwWilsonCowanPlastic.py:140-158; np.corrcoef
 whole_sweep_both.py:81; utils.get_all_metrics / kuramoto utils.py:34-50; Welch
-peak whole_sweep_both.py:90-95.  Every array stays on the device; columns are
-c = b*N + n.
+peak whole_sweep_both.py:90-95; utils.envelope utils.py:145-154.  Every array
+stays on the device; columns are c = b*N + n.
 """
 from __future__ import annotations
 
 import ctypes
+import functools
 
 import numpy as np
 import torch
@@ -115,6 +117,76 @@ def hilbert_phase_long(x, out=None, ws_bytes=None):
     _lib.check(L.wc_hilbert_phase_long(C, M, _lib.ptr(x.contiguous()), _lib.ptr(ph), _lib.ptr(ws), ws_bytes,
                                        _lib.stream_handle()), "wc_hilbert_phase_long")
     return ph
+
+
+def hilbert_envelope(x, method=0, ws_bytes=None):
+    """|hilbert(x, axis=0)| for x [M][C] fp64, 2 <= M <= 524288 -> [M][C] (wc_hilbert_envelope).
+
+    method: 0 = the faster of the two (direct below M = 2048, long from there on), 1 = the direct
+    convolution (M <= 8192), 2 = the Bluestein FFT.  ws_bytes (long method only): workspace size
+    (default: what all C columns want, at most HILBERT_LONG_WS_CAP, never below the minimum); the
+    result does not depend on it."""
+    L = _lib.lib()
+    M, C = x.shape
+    need = L.wc_hilbert_envelope_workspace_size(C, M, method)
+    if need == 0:
+        raise _lib.WCSDEError(f"hilbert_envelope: M = {M} outside 2 .. 524288 (8192 for method 1), no columns "
+                              f"or method = {method} not 0, 1, 2")
+    if need == M * 8:  # the direct method: q[0..M), nothing to gain from more
+        ws_bytes = need
+    elif ws_bytes is None:
+        fft_len = max(1 << 15, 1 << (2 * M - 2).bit_length())  # max(2^15, nextpow2(2 M - 1))
+        ws_bytes = max(need, min(need + (C - 1) * 32 * fft_len, HILBERT_LONG_WS_CAP))
+    x = x.contiguous()
+    env = torch.empty((M, C), dtype=torch.float64, device=x.device)
+    ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.float64, device=x.device)
+    _lib.check(L.wc_hilbert_envelope(C, M, _lib.ptr(x), _lib.ptr(env), method, _lib.ptr(ws), ws_bytes,
+                                     _lib.stream_handle()), "wc_hilbert_envelope")
+    return env
+
+
+def filtfilt(b, a, x):
+    """scipy.signal.filtfilt(b, a, x, axis=0) for a device [T][C] or [T][B][N] fp64 tensor
+    (wc_filtfilt: orders 1 .. 8, default padlen 3 (order + 1) < T, lfilter_zi initial conditions);
+    b, a host coefficient arrays of equal length, a[0] == 1.  Returns a new tensor of x's shape."""
+    b = np.asarray(b, dtype=np.float64)
+    a = np.asarray(a, dtype=np.float64)
+    if b.ndim != 1 or b.shape != a.shape:
+        raise ValueError("filtfilt: b and a must be 1-D arrays of the same length")
+    if x.dtype != torch.float64 or x.dim() < 2:
+        raise TypeError("filtfilt: x must be a [T][C] or [T][B][N] fp64 device tensor")
+    zi = lfilter_zi(b, a)
+    x = x.contiguous()
+    y = torch.empty_like(x)
+    T = x.shape[0]
+    dp = lambda v: (ctypes.c_double * len(v))(*[float(t) for t in v])  # noqa: E731
+    _lib.check(_lib.lib().wc_filtfilt(len(a) - 1, dp(b), dp(a), dp(zi), T, x.numel() // T, _lib.ptr(x), _lib.ptr(y),
+                                      _lib.stream_handle()), "wc_filtfilt")
+    return y
+
+
+@functools.lru_cache(maxsize=16)
+def envelope_filters(dt, fmin, fmax, fcut):
+    """utils.envelope's two designs (utils.py:147, 151): signal.bessel(3, [2 dt fmin, 2 dt fmax],
+    'bandpass') and, for a truthy fcut, signal.bessel(3, [2 dt fcut], 'low') (else None), as (b, a)
+    pairs.  SciPy's own design routines, as optimize_sc.band and for its reason: in (b, a) form the
+    last bits of the coefficients matter (a restated design moved the envelope by 2e-8 .. 4e-7 of
+    its scale)."""
+    from scipy import signal
+    bp = signal.bessel(3, [2 * dt * fmin, 2 * dt * fmax], btype="bandpass")
+    lp = signal.bessel(3, [2 * dt * fcut], btype="low") if fcut else None
+    return bp, lp
+
+
+def envelope(x, dt=0.002, freqs=(8, 13), fcut=None):
+    """utils.envelope (utils.py:145-154) on the device: Bessel order-3 band-pass filtfilt over
+    freqs (Hz, at sampling step dt), |hilbert| along time and, for a truthy fcut, a Bessel order-3
+    low-pass filtfilt at fcut Hz.  x [T][C] or [T][B][N] fp64 -> a tensor of x's shape."""
+    fmin, fmax = freqs
+    (bb, ba), lp = envelope_filters(float(dt), float(fmin), float(fmax), float(fcut) if fcut else None)
+    T = x.shape[0]
+    env = hilbert_envelope(filtfilt(bb, ba, x).reshape(T, -1)).reshape(x.shape)
+    return filtfilt(lp[0], lp[1], env) if lp is not None else env
 
 
 def fc_metrics(bold=None, B=None, N=None, empfc=None, fc_in=None, kuramoto=True, want_fc=False, data_range=1.0):

@@ -1,12 +1,13 @@
-"""Drop-in for the FC/observable part of utils.py (utils.py:18-50).
+"""Drop-in for utils.py's observables and matrix helpers (utils.py:18-74, 134-154).
 
-get_all_metrics and kuramoto run in libwcsde.so (wc_fc_metrics,
-wc_hilbert_phase / wc_hilbert_phase_long + wc_kuramoto); the small array helpers the reference defines
-next to them (flat_FC, new_metric, cohen_d) are kept as host numpy one-liners
-for callers that import them.  Plotting/analysis helpers of utils.py
-(sub_weight, cortex_mat, RSN_profile_FC, find_extreme, xy2plotcor,
-fill_missing, scale_mat, envelope) are not on the sweep path
-and are not mirrored.
+get_all_metrics, kuramoto and envelope run in libwcsde.so (wc_fc_metrics,
+wc_hilbert_phase / wc_hilbert_phase_long + wc_kuramoto, wc_filtfilt +
+wc_hilbert_envelope); the small array helpers the reference defines next to
+them (flat_FC, new_metric, cohen_d, sub_weight, cortex_mat, scale_mat and the
+thal / sub / cortex index lists) are host numpy for callers that import them.
+Not mirrored: RSN_profile_FC and fill_missing (they cannot run upstream: the
+RSN index table is commented out, DataFrame.append is gone from pandas) and
+the pandas / plot helpers find_extreme and xy2plotcor.
 """
 import numpy as np
 import torch
@@ -33,6 +34,52 @@ def flat_FC(FC):
 def new_metric(flat1, flat2):
     """utils.py:28-31."""
     return 1 - np.corrcoef(flat1, flat2)[0, 1] + (flat1.mean() - flat2.mean()) ** 2
+
+
+thal = [38, 51]
+not_thal = [i for i in range(90) if i not in thal]
+subL, subR = [35, 36, 37, 38], [51, 52, 53, 54]
+sub = subL + subR
+cortex = [i for i in range(90) if i not in sub]
+
+
+def sub_weight(struct, prop=1):
+    """utils.py:58-67 -- the subcortical rows and columns of struct times prop (a proportion of
+    the original), the links among subcortical areas left as they are."""
+    struct = np.asarray(struct)
+    is_sub = np.zeros(len(struct), dtype=bool)
+    is_sub[sub] = True
+    one_end = is_sub[:, None] ^ is_sub[None, :]  # cortex <-> subcortex links, either direction
+    out = np.copy(struct)
+    out[one_end] = (prop * struct)[one_end]
+    return out
+
+
+def cortex_mat(mat90):
+    """utils.py:70-74 -- the 82 x 82 cortical block of a 90 x 90 AAL matrix."""
+    return np.asarray(mat90)[np.ix_(cortex, cortex)]
+
+
+def scale_mat(struct, G, subG):
+    """utils.py:137-143 -- thalamic columns of struct times subG, every other column times G
+    (scalars, or vectors over the rows)."""
+    struct = np.asarray(struct)
+    out = np.copy(struct)
+    for area in range(struct.shape[1]):
+        out[:, area] = (subG if area in thal else G) * struct[:, area]
+    return out
+
+
+def envelope(series, dt=0.002, freqs=[8, 13], fcut=None):
+    """utils.py:145-154: band-limited amplitude envelope of series (time, rois): Bessel order-3
+    band-pass filtfilt over freqs, |hilbert| along time and, for a truthy fcut, a Bessel order-3
+    low-pass filtfilt at fcut.  numpy in, numpy out; a 1-D series gives a 1-D envelope.
+    22 <= time <= 524288 (the order-6 band-pass's padlen is 21)."""
+    x = np.ascontiguousarray(series, dtype=np.float64)
+    if x.ndim not in (1, 2):
+        raise ValueError("series must be (time,) or (time, rois)")
+    xt = torch.as_tensor(x.reshape(x.shape[0], -1)).to(device)
+    return sigchain.envelope(xt, dt, tuple(freqs), fcut).cpu().numpy().reshape(x.shape)
 
 
 def kuramoto(sign):
