@@ -324,6 +324,31 @@ int wc_welch_accumulate(int B, int N, const void* E, int e_f64, int64_t ld, int6
 int wc_welch_peak(int B, int N, int nseg, double fs, const double* acc, double* peak, double* psd,
                   void* stream);
 
+/* scipy.signal.welch(x, axis=0) of every column of a time-major x [T][C] fp64 ->
+ * psd [nperseg/2 + 1][C] fp64 (cortex_run.py:203-209), for return_onesided=True,
+ * average='mean', nfft=None: segments of nperseg samples every
+ * step = nperseg - noverlap, nseg = (T - nperseg) / step + 1 of them (trailing
+ * samples are ignored); per segment the mean is subtracted (detrend 1) or not
+ * (detrend 0), the segment is multiplied by window [nperseg] (DEVICE, fp64) and
+ * |DFT|^2 taken at bins 0 .. nperseg/2; the mean over segments times scale (the
+ * caller's 1 / (fs sum w^2) for a density, 1 / (sum w)^2 for a spectrum) is
+ * doubled at every bin but 0 and, for even nperseg, nperseg/2.
+ * 2 <= nperseg <= 4096 (any value: the exact DFT is a Bluestein convolution over
+ * an FFT of max(64, nextpow2(2 nperseg - 1)) points in one workgroup's LDS,
+ * wc_welch_psd.hip; larger returns WC_EUNSUPPORTED), 0 <= noverlap < nperseg,
+ * T >= nperseg, C >= 1; psd must not alias x; x, window, psd 8-byte and the
+ * workspace 16-byte aligned.  wc_welch_psd_workspace_size is the minimum: the
+ * tables (W_8192, the chirp and its spectrum) and the per-block sums of one
+ * column, NB (nperseg/2 + 1) doubles with NB <= 16 segment blocks fixed by
+ * (T, nperseg, noverlap); every further such slice lets one more column be in
+ * flight per pass (up to C).  No atomics: a column's PSD is bit-identical for
+ * every C, every position of the column and every workspace size.  The size
+ * function returns 0 where the call would not return WC_OK or WC_EWORKSPACE. */
+size_t wc_welch_psd_workspace_size(int64_t C, int64_t T, int nperseg, int noverlap);
+int wc_welch_psd(int64_t C, int64_t T, const double* x, int nperseg, int noverlap,
+                 const double* window, int detrend, double scale, double* psd,
+                 void* workspace, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,10 +1,11 @@
 """Device-side signal chain: BOLD + band-pass filtfilt + decimation, FC and
-goodness of fit, Kuramoto, Welch peak, band-limited amplitude envelopes -- thin
-wrappers over libwcsde.so.
+goodness of fit, Kuramoto, Welch peak, band-limited amplitude envelopes, Welch
+spectra per column -- thin wrappers over libwcsde.so.
 
 References: simBOLD netwWilsonCowanPlastic.py:140-158; np.corrcoef
 whole_sweep_both.py:81; utils.get_all_metrics / kuramoto utils.py:34-50; Welch
-peak whole_sweep_both.py:90-95; utils.envelope utils.py:145-154.  Every array
+peak whole_sweep_both.py:90-95; utils.envelope utils.py:145-154; signal.welch
+cortex_run.py:203-209.  Every array
 stays on the device; columns are c = b*N + n.
 """
 from __future__ import annotations
@@ -327,6 +328,95 @@ def welch_peak(E_t, fs=500.0, want_psd=False):
     for s in range(nseg):
         wa.accumulate(nodemajor, T, T, 1, s * WELCH_HOP)
     return wa.peak(fs, want_psd)
+
+
+WELCH_PSD_WS_CAP = 1 << 30     # wc_welch_psd: workspace ceiling (column tiles beyond it)
+
+
+@functools.lru_cache(maxsize=16)
+def _welch_window(window, nperseg, device):
+    """scipy.signal.get_window(window, nperseg) (periodic, as signal.welch's) on the device, with the
+    host sums the scalings need: (tensor [nperseg], sum w^2, (sum w)^2).  window: a name or a
+    (name, parameter, ...) tuple."""
+    from scipy import signal
+    return _welch_window_upload(signal.get_window(window, nperseg), device)
+
+
+def _welch_window_upload(win, device):
+    win = np.ascontiguousarray(win, dtype=np.float64)
+    return torch.as_tensor(win).to(device), float((win * win).sum()), float(win.sum() ** 2)
+
+
+def welch(x, fs=1.0, window="hann", nperseg=None, noverlap=None, detrend="constant", scaling="density",
+          ws_bytes=None):
+    """scipy.signal.welch(x, fs, window, nperseg, noverlap, detrend=detrend, scaling=scaling, axis=0)
+    of a device tensor x [T][C] or [T][B][N] fp64 (wc_welch_psd: one-sided, mean over segments,
+    2 <= nperseg <= 4096) -> (freqs, psd): freqs a numpy array [F], F = nperseg // 2 + 1, psd a
+    device tensor [F][C] or [F][B][N].
+
+    window: a SciPy window name or (name, parameter) tuple, or an array of nperseg weights.
+    SciPy's defaults and coercions: nperseg None -> 256 (an array window: its length), noverlap
+    None -> nperseg // 2, both through int(); a named window with nperseg > T is clamped to T with
+    SciPy's UserWarning.  detrend: "constant" or False.  scaling: "density" or "spectrum".
+    ws_bytes: workspace size (default: what all columns want, at most WELCH_PSD_WS_CAP, never
+    below the minimum); the result does not depend on it."""
+    import warnings
+    from scipy import fft as sp_fft
+    if x.dtype != torch.float64 or x.dim() < 2:
+        raise TypeError("welch: x must be a [T][C] or [T][B][N] fp64 device tensor")
+    if detrend == "constant":
+        det = 1
+    elif detrend is False:
+        det = 0
+    else:
+        raise NotImplementedError(f"welch: detrend = {detrend!r} (only 'constant' and False run on the device)")
+    if scaling not in ("density", "spectrum"):
+        raise ValueError(f"Unknown scaling: {scaling!r}")
+    T = x.shape[0]
+    if nperseg is not None:
+        nperseg = int(nperseg)
+        if nperseg < 1:
+            raise ValueError("nperseg must be a positive integer")
+    if isinstance(window, (str, tuple)):
+        if nperseg is None:
+            nperseg = 256
+        if nperseg > T:
+            warnings.warn(f"nperseg = {nperseg:d} is greater than input length  = {T:d}, using nperseg = {T:d}",
+                          stacklevel=2)
+            nperseg = T
+        win, sw2, s2w = _welch_window(window, nperseg, str(x.device))
+    else:
+        w = np.asarray(window)
+        if w.ndim != 1:
+            raise ValueError("window must be 1-D")
+        if T < w.shape[0]:
+            raise ValueError("window is longer than input signal")
+        if nperseg is None:
+            nperseg = w.shape[0]
+        elif nperseg != w.shape[0]:
+            raise ValueError("value specified for nperseg is different from length of window")
+        win, sw2, s2w = _welch_window_upload(w, x.device)
+    noverlap = nperseg // 2 if noverlap is None else int(noverlap)
+    if noverlap >= nperseg:
+        raise ValueError("noverlap must be less than nperseg.")
+    scale = 1.0 / (fs * sw2) if scaling == "density" else 1.0 / s2w
+    freqs = sp_fft.rfftfreq(nperseg, 1 / fs)
+
+    L = _lib.lib()
+    x2 = x.reshape(T, -1).contiguous()
+    C = x2.shape[1]
+    F = nperseg // 2 + 1
+    need = L.wc_welch_psd_workspace_size(C, T, nperseg, noverlap)
+    if ws_bytes is None and need:
+        nseg = (T - nperseg) // (nperseg - noverlap) + 1
+        sb = 2 * -(-nseg // 32)                   # segments per block; -(-nseg // sb) blocks of F doubles a column
+        ws_bytes = max(need, min(need + (C - 1) * -(-nseg // sb) * F * 8, WELCH_PSD_WS_CAP))
+    ws_bytes = ws_bytes or 16                     # need == 0: the call says why
+    psd = torch.empty((F, C), dtype=torch.float64, device=x.device)
+    ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.float64, device=x.device)
+    _lib.check(L.wc_welch_psd(C, T, _lib.ptr(x2), nperseg, noverlap, _lib.ptr(win), det, scale, _lib.ptr(psd),
+                              _lib.ptr(ws), ws_bytes, _lib.stream_handle()), "wc_welch_psd")
+    return freqs, psd.reshape((F,) + tuple(x.shape[1:]))
 
 
 def sim_bold(E_t, bold_downsamp=1000, neq=NEQ, bold_dt=0.04):

@@ -2,7 +2,8 @@
 
 get_all_metrics, kuramoto and envelope run in libwcsde.so (wc_fc_metrics,
 wc_hilbert_phase / wc_hilbert_phase_long + wc_kuramoto, wc_filtfilt +
-wc_hilbert_envelope); the small array helpers the reference defines next to
+wc_hilbert_envelope), and so does welch, a stand-in for the scipy.signal.welch
+that cortex_run.py:203-209 calls next to them (wc_welch_psd); the small array helpers the reference defines next to
 them (flat_FC, new_metric, cohen_d, sub_weight, cortex_mat, scale_mat and the
 thal / sub / cortex index lists) are host numpy for callers that import them.
 Not mirrored: RSN_profile_FC and fill_missing (they cannot run upstream: the
@@ -80,6 +81,38 @@ def envelope(series, dt=0.002, freqs=[8, 13], fcut=None):
         raise ValueError("series must be (time,) or (time, rois)")
     xt = torch.as_tensor(x.reshape(x.shape[0], -1)).to(device)
     return sigchain.envelope(xt, dt, tuple(freqs), fcut).cpu().numpy().reshape(x.shape)
+
+
+def welch(x, fs=1.0, window='hann', nperseg=None, noverlap=None, nfft=None, detrend='constant',
+          return_onesided=True, scaling='density', axis=-1, average='mean'):
+    """scipy.signal.welch with its parameter order and defaults, on the device (wc_welch_psd), for
+    what cortex_run.py:203-209 asks of it: real input, one-sided, mean over segments, no nfft
+    padding, detrend 'constant' or False, 2 <= nperseg <= 4096.  numpy in, numpy (freqs, Pxx) out,
+    shaped as SciPy's; anything else SciPy's welch offers raises NotImplementedError."""
+    if nfft is not None:
+        named = isinstance(window, (str, tuple))
+        seg = int(nperseg) if nperseg is not None else (256 if named else len(window))
+        if named:
+            seg = min(seg, np.shape(x)[axis])  # SciPy clamps a named window's nperseg to the input
+    if nfft is not None and int(nfft) != seg:
+        raise NotImplementedError("welch: nfft other than nperseg (zero padding) does not run on the device")
+    if not return_onesided:
+        raise NotImplementedError("welch: return_onesided=False does not run on the device")
+    if average != 'mean':
+        raise NotImplementedError(f"welch: average = {average!r} (only 'mean' runs on the device)")
+    if not (detrend is False or (isinstance(detrend, str) and detrend == 'constant')):
+        raise NotImplementedError(f"welch: detrend = {detrend!r} (only 'constant' and False run on the device)")
+    x = np.asarray(x)
+    if np.iscomplexobj(x):
+        raise NotImplementedError("welch: complex input x does not run on the device")
+    if x.ndim < 1 or x.size == 0:
+        raise ValueError("welch: x must have at least one sample")
+    xt = np.moveaxis(x, axis, 0)
+    rest = xt.shape[1:]
+    xd = torch.as_tensor(np.ascontiguousarray(xt.reshape(xt.shape[0], -1), dtype=np.float64)).to(device)
+    freqs, psd = sigchain.welch(xd, fs, window, nperseg, noverlap, detrend, scaling)
+    pxx = psd.cpu().numpy().reshape((psd.shape[0],) + rest)
+    return freqs, np.moveaxis(pxx, 0, axis) if rest else pxx
 
 
 def kuramoto(sign):
