@@ -349,6 +349,40 @@ int wc_welch_psd(int64_t C, int64_t T, const double* x, int nperseg, int noverla
                  const double* window, int detrend, double scale, double* psd,
                  void* workspace, size_t ws_bytes, void* stream);
 
+/* scipy.signal.csd / coherence between the columns of a time-major x [T][C] fp64
+ * (wc_csd.hip): wc_welch_psd's segments, window, detrend, scale and one-sided
+ * doubling, P_ij[f] = mean over segments of conj(X_i[f]) X_j[f] (SciPy's sign),
+ * F = nperseg/2 + 1 bins.  mode selects the output:
+ *   WC_CSD_MATRIX          out [F][C][C] complex, interleaved (re, im): exactly
+ *                          Hermitian, the diagonal (the columns' PSDs) exactly real;
+ *   WC_CSD_COHERENCE       out [F][C][C] real, |P_ij|^2 / (P_ii P_jj): exactly
+ *                          symmetric (scale is validated but cancels);
+ *   WC_CSD_PAIRS           out [F][C/2] complex, column i against column i + C/2
+ *                          (csd(x, y) of equally shaped x and y, stacked [x | y]);
+ *   WC_CSD_PAIR_COHERENCE  out [F][C/2] real, the pairs' coherence.
+ * Plain IEEE division: a column without power gives NaN coherence, as SciPy.
+ * 2 <= nperseg <= 4096 (larger: WC_EUNSUPPORTED), 0 <= noverlap < nperseg,
+ * T >= nperseg, 1 <= C <= 2^24; the matrix modes take C <= 1024 (more:
+ * WC_EUNSUPPORTED), the pair modes an even C; out must not alias x; x, window, out
+ * 8-byte and the workspace 16-byte aligned.
+ * wc_csd_workspace_size is the minimum, whatever the mode: the tables of
+ * wc_welch_psd, F C 16 bytes of running sums, and the complex spectra of one
+ * segment block (two segments, the pair that shares a transform) of all C columns,
+ * 2 F C 16 bytes; every further segment block lets two more segments go through the
+ * two passes at a time (up to all).  No atomics: the segments are added in one
+ * order fixed by (T, nperseg, noverlap), a later chunk continues the running sum,
+ * and the result is bit-identical for every workspace size and from run to run; an
+ * entry depends on the samples of its own two columns only.  The size function
+ * returns 0 for a shape the call rejects (the mode's own limits apart). */
+#define WC_CSD_MATRIX 0
+#define WC_CSD_COHERENCE 1
+#define WC_CSD_PAIRS 2
+#define WC_CSD_PAIR_COHERENCE 3
+size_t wc_csd_workspace_size(int64_t C, int64_t T, int nperseg, int noverlap);
+int wc_csd(int64_t C, int64_t T, const double* x, int nperseg, int noverlap,
+           const double* window, int detrend, double scale, int mode, double* out,
+           void* workspace, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

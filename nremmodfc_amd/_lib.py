@@ -85,6 +85,8 @@ _SIGNATURES = {
     "wc_welch_peak": (c_int, [c_int, c_int, c_int, c_dbl, c_vp, c_vp, c_vp, c_vp]),
     "wc_welch_psd_workspace_size": (c_sz, [c_i64, c_i64, c_int, c_int]),
     "wc_welch_psd": (c_int, [c_i64, c_i64, c_vp, c_int, c_int, c_vp, c_int, c_dbl, c_vp, c_vp, c_sz, c_vp]),
+    "wc_csd_workspace_size": (c_sz, [c_i64, c_i64, c_int, c_int]),
+    "wc_csd": (c_int, [c_i64, c_i64, c_vp, c_int, c_int, c_vp, c_int, c_dbl, c_int, c_vp, c_vp, c_sz, c_vp]),
 }
 
 

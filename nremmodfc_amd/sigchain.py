@@ -1,6 +1,7 @@
 """Device-side signal chain: BOLD + band-pass filtfilt + decimation, FC and
 goodness of fit, Kuramoto, Welch peak, band-limited amplitude envelopes, Welch
-spectra per column -- thin wrappers over libwcsde.so.
+spectra per column, cross spectra and coherence between columns -- thin
+wrappers over libwcsde.so.
 
 References: simBOLD netwWilsonCowanPlastic.py:140-158; np.corrcoef
 whole_sweep_both.py:81; utils.get_all_metrics / kuramoto utils.py:34-50; Welch
@@ -347,6 +348,50 @@ def _welch_window_upload(win, device):
     return torch.as_tensor(win).to(device), float((win * win).sum()), float(win.sum() ** 2)
 
 
+def _welch_args(name, T, device, fs, window, nperseg, noverlap, detrend, scaling, stacklevel=3):
+    """SciPy's coercion of the arguments welch, csd and coherence share, for a series of T samples ->
+    (detrend flag, window tensor [nperseg], nperseg, noverlap, scale, freqs); name prefixes the
+    messages; stacklevel makes the clamped-nperseg warning point at the public function's caller."""
+    import warnings
+    from scipy import fft as sp_fft
+    if detrend == "constant":
+        det = 1
+    elif detrend is False:
+        det = 0
+    else:
+        raise NotImplementedError(f"{name}: detrend = {detrend!r} (only 'constant' and False run on the device)")
+    if scaling not in ("density", "spectrum"):
+        raise ValueError(f"Unknown scaling: {scaling!r}")
+    if nperseg is not None:
+        nperseg = int(nperseg)
+        if nperseg < 1:
+            raise ValueError("nperseg must be a positive integer")
+    if isinstance(window, (str, tuple)):
+        if nperseg is None:
+            nperseg = 256
+        if nperseg > T:
+            warnings.warn(f"nperseg = {nperseg:d} is greater than input length  = {T:d}, using nperseg = {T:d}",
+                          stacklevel=stacklevel)
+            nperseg = T
+        win, sw2, s2w = _welch_window(window, nperseg, str(device))
+    else:
+        w = np.asarray(window)
+        if w.ndim != 1:
+            raise ValueError("window must be 1-D")
+        if T < w.shape[0]:
+            raise ValueError("window is longer than input signal")
+        if nperseg is None:
+            nperseg = w.shape[0]
+        elif nperseg != w.shape[0]:
+            raise ValueError("value specified for nperseg is different from length of window")
+        win, sw2, s2w = _welch_window_upload(w, device)
+    noverlap = nperseg // 2 if noverlap is None else int(noverlap)
+    if noverlap >= nperseg:
+        raise ValueError("noverlap must be less than nperseg.")
+    scale = 1.0 / (fs * sw2) if scaling == "density" else 1.0 / s2w
+    return det, win, nperseg, noverlap, scale, sp_fft.rfftfreq(nperseg, 1 / fs)
+
+
 def welch(x, fs=1.0, window="hann", nperseg=None, noverlap=None, detrend="constant", scaling="density",
           ws_bytes=None):
     """scipy.signal.welch(x, fs, window, nperseg, noverlap, detrend=detrend, scaling=scaling, axis=0)
@@ -360,47 +405,11 @@ def welch(x, fs=1.0, window="hann", nperseg=None, noverlap=None, detrend="consta
     SciPy's UserWarning.  detrend: "constant" or False.  scaling: "density" or "spectrum".
     ws_bytes: workspace size (default: what all columns want, at most WELCH_PSD_WS_CAP, never
     below the minimum); the result does not depend on it."""
-    import warnings
-    from scipy import fft as sp_fft
     if x.dtype != torch.float64 or x.dim() < 2:
         raise TypeError("welch: x must be a [T][C] or [T][B][N] fp64 device tensor")
-    if detrend == "constant":
-        det = 1
-    elif detrend is False:
-        det = 0
-    else:
-        raise NotImplementedError(f"welch: detrend = {detrend!r} (only 'constant' and False run on the device)")
-    if scaling not in ("density", "spectrum"):
-        raise ValueError(f"Unknown scaling: {scaling!r}")
     T = x.shape[0]
-    if nperseg is not None:
-        nperseg = int(nperseg)
-        if nperseg < 1:
-            raise ValueError("nperseg must be a positive integer")
-    if isinstance(window, (str, tuple)):
-        if nperseg is None:
-            nperseg = 256
-        if nperseg > T:
-            warnings.warn(f"nperseg = {nperseg:d} is greater than input length  = {T:d}, using nperseg = {T:d}",
-                          stacklevel=2)
-            nperseg = T
-        win, sw2, s2w = _welch_window(window, nperseg, str(x.device))
-    else:
-        w = np.asarray(window)
-        if w.ndim != 1:
-            raise ValueError("window must be 1-D")
-        if T < w.shape[0]:
-            raise ValueError("window is longer than input signal")
-        if nperseg is None:
-            nperseg = w.shape[0]
-        elif nperseg != w.shape[0]:
-            raise ValueError("value specified for nperseg is different from length of window")
-        win, sw2, s2w = _welch_window_upload(w, x.device)
-    noverlap = nperseg // 2 if noverlap is None else int(noverlap)
-    if noverlap >= nperseg:
-        raise ValueError("noverlap must be less than nperseg.")
-    scale = 1.0 / (fs * sw2) if scaling == "density" else 1.0 / s2w
-    freqs = sp_fft.rfftfreq(nperseg, 1 / fs)
+    det, win, nperseg, noverlap, scale, freqs = _welch_args("welch", T, x.device, fs, window, nperseg, noverlap,
+                                                            detrend, scaling)
 
     L = _lib.lib()
     x2 = x.reshape(T, -1).contiguous()
@@ -417,6 +426,54 @@ def welch(x, fs=1.0, window="hann", nperseg=None, noverlap=None, detrend="consta
     _lib.check(L.wc_welch_psd(C, T, _lib.ptr(x2), nperseg, noverlap, _lib.ptr(win), det, scale, _lib.ptr(psd),
                               _lib.ptr(ws), ws_bytes, _lib.stream_handle()), "wc_welch_psd")
     return freqs, psd.reshape((F,) + tuple(x.shape[1:]))
+
+
+CSD_WS_CAP = 1 << 30           # wc_csd: workspace ceiling (segment chunks beyond it)
+CSD_MATRIX, CSD_COHERENCE, CSD_PAIRS, CSD_PAIR_COHERENCE = 0, 1, 2, 3
+
+
+def _csd(name, coh, x, y, fs, window, nperseg, noverlap, detrend, scaling, ws_bytes):
+    if x.dtype != torch.float64 or x.dim() != 2:
+        raise TypeError(f"{name}: x must be a [T][C] fp64 device tensor")
+    if y is not None and (y.dtype != torch.float64 or y.shape != x.shape or y.device != x.device):
+        raise TypeError(f"{name}: y must be an fp64 tensor of x's shape on x's device")
+    T = x.shape[0]
+    det, win, nperseg, noverlap, scale, freqs = _welch_args(name, T, x.device, fs, window, nperseg, noverlap,
+                                                            detrend, scaling, stacklevel=4)
+    L = _lib.lib()
+    x2 = (x if y is None else torch.cat((x, y), dim=1)).contiguous()  # pairs: column i with i + C
+    C = x2.shape[1]
+    F = nperseg // 2 + 1
+    mode = (CSD_COHERENCE if coh else CSD_MATRIX) if y is None else (CSD_PAIR_COHERENCE if coh else CSD_PAIRS)
+    need = L.wc_csd_workspace_size(C, T, nperseg, noverlap)
+    if ws_bytes is None and need:
+        nseg = (T - nperseg) // (nperseg - noverlap) + 1
+        ws_bytes = max(need, min(need + (-(-nseg // 2) - 1) * 2 * F * C * 16, CSD_WS_CAP))  # all segment pairs
+    ws_bytes = ws_bytes or 16                     # need == 0: the call says why
+    shape = (F, x.shape[1], x.shape[1]) if y is None else (F, x.shape[1])
+    out = torch.empty(shape, dtype=torch.float64 if coh else torch.complex128, device=x.device)
+    ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.float64, device=x.device)
+    _lib.check(L.wc_csd(C, T, _lib.ptr(x2), nperseg, noverlap, _lib.ptr(win), det, scale, mode, _lib.ptr(out),
+                        _lib.ptr(ws), ws_bytes, _lib.stream_handle()), "wc_csd")
+    return freqs, out
+
+
+def csd(x, y=None, fs=1.0, window="hann", nperseg=None, noverlap=None, detrend="constant", scaling="density",
+        ws_bytes=None):
+    """Cross-spectral density (wc_csd) of a device tensor x [T][C] fp64 with welch's arguments and
+    coercions -> (freqs, P), P complex128 on the device.  y None: the matrix between x's columns,
+    P [F][C][C] with P[f][i][j] = scipy.signal.csd(x[:, i], x[:, j])[1][f] (C <= 1024; exactly
+    Hermitian, the diagonal welch's PSDs).  y of x's shape: columnwise, P [F][C] =
+    scipy.signal.csd(x, y, axis=0).  ws_bytes: workspace size (default: what all segments want, at
+    most CSD_WS_CAP, never below the minimum); the result does not depend on it."""
+    return _csd("csd", False, x, y, fs, window, nperseg, noverlap, detrend, scaling, ws_bytes)
+
+
+def coherence(x, y=None, fs=1.0, window="hann", nperseg=None, noverlap=None, detrend="constant", ws_bytes=None):
+    """Magnitude-squared coherence |P_xy|^2 / (P_xx P_yy) (wc_csd), arguments and shapes as csd's,
+    real fp64 on the device: [F][C][C] between x's columns (y None), [F][C] =
+    scipy.signal.coherence(x, y, axis=0) otherwise.  A column without power gives NaN, as SciPy."""
+    return _csd("coherence", True, x, y, fs, window, nperseg, noverlap, detrend, "density", ws_bytes)
 
 
 def sim_bold(E_t, bold_downsamp=1000, neq=NEQ, bold_dt=0.04):

@@ -3,7 +3,8 @@
 get_all_metrics, kuramoto and envelope run in libwcsde.so (wc_fc_metrics,
 wc_hilbert_phase / wc_hilbert_phase_long + wc_kuramoto, wc_filtfilt +
 wc_hilbert_envelope), and so does welch, a stand-in for the scipy.signal.welch
-that cortex_run.py:203-209 calls next to them (wc_welch_psd); the small array helpers the reference defines next to
+that cortex_run.py:203-209 calls next to them (wc_welch_psd), with csd, coherence, csd_matrix and coherence_matrix for
+the coupling between regions per frequency (wc_csd); the small array helpers the reference defines next to
 them (flat_FC, new_metric, cohen_d, sub_weight, cortex_mat, scale_mat and the
 thal / sub / cortex index lists) are host numpy for callers that import them.
 Not mirrored: RSN_profile_FC and fill_missing (they cannot run upstream: the
@@ -113,6 +114,88 @@ def welch(x, fs=1.0, window='hann', nperseg=None, noverlap=None, nfft=None, detr
     freqs, psd = sigchain.welch(xd, fs, window, nperseg, noverlap, detrend, scaling)
     pxx = psd.cpu().numpy().reshape((psd.shape[0],) + rest)
     return freqs, np.moveaxis(pxx, 0, axis) if rest else pxx
+
+
+def _cross_input(name, x, y, window, nperseg, nfft, detrend, axis, return_onesided=True, average='mean'):
+    """What csd and coherence refuse before they touch the device, and x, y as (time, columns)
+    device tensors with the shape of the remaining axes."""
+    x, y = np.asarray(x), np.asarray(y)
+    if np.iscomplexobj(x) or np.iscomplexobj(y):
+        raise NotImplementedError(f"{name}: complex input does not run on the device")
+    if x.shape != y.shape:
+        raise NotImplementedError(f"{name}: x and y of different shapes or lengths (broadcasting, zero padding of the "
+                                  "shorter) do not run on the device")
+    if x.ndim < 1 or x.size == 0:
+        raise ValueError(f"{name}: x must have at least one sample")
+    if nfft is not None:
+        named = isinstance(window, (str, tuple))
+        seg = int(nperseg) if nperseg is not None else (256 if named else len(window))
+        if named:
+            seg = min(seg, x.shape[axis])  # SciPy clamps a named window's nperseg to the input
+        if int(nfft) != seg:
+            raise NotImplementedError(f"{name}: nfft other than nperseg (zero padding) does not run on the device")
+    if not return_onesided:
+        raise NotImplementedError(f"{name}: return_onesided=False does not run on the device")
+    if average != 'mean':
+        raise NotImplementedError(f"{name}: average = {average!r} (only 'mean' runs on the device)")
+    if not (detrend is False or (isinstance(detrend, str) and detrend == 'constant')):
+        raise NotImplementedError(f"{name}: detrend = {detrend!r} (only 'constant' and False run on the device)")
+    xt, yt = np.moveaxis(x, axis, 0), np.moveaxis(y, axis, 0)
+    rest = xt.shape[1:]
+    up = lambda a: torch.from_numpy(np.array(a.reshape(a.shape[0], -1), dtype=np.float64, order="C")).to(device)
+    return up(xt), up(yt), rest
+
+
+def _cross_output(out, rest, axis):
+    p = out.cpu().numpy().reshape((out.shape[0],) + rest)
+    return np.moveaxis(p, 0, axis) if rest else p
+
+
+def csd(x, y, fs=1.0, window='hann', nperseg=None, noverlap=None, nfft=None, detrend='constant',
+        return_onesided=True, scaling='density', axis=-1, average='mean'):
+    """scipy.signal.csd with its parameter order and defaults, on the device (wc_csd's pair mode),
+    for equally shaped real x and y: one-sided, mean over segments, no nfft padding, detrend
+    'constant' or False, 2 <= nperseg <= 4096.  numpy in, numpy (freqs, Pxy) out, complex, shaped as
+    SciPy's; anything else SciPy's csd offers raises NotImplementedError."""
+    xd, yd, rest = _cross_input("csd", x, y, window, nperseg, nfft, detrend, axis, return_onesided, average)
+    freqs, p = sigchain.csd(xd, yd, fs, window, nperseg, noverlap, detrend, scaling)
+    return freqs, _cross_output(p, rest, axis)
+
+
+def coherence(x, y, fs=1.0, window='hann', nperseg=None, noverlap=None, nfft=None, detrend='constant', axis=-1):
+    """scipy.signal.coherence with its parameter order and defaults, on the device (wc_csd's pair
+    mode), under csd's restrictions.  numpy in, numpy (freqs, Cxy) out."""
+    xd, yd, rest = _cross_input("coherence", x, y, window, nperseg, nfft, detrend, axis)
+    freqs, c = sigchain.coherence(xd, yd, fs, window, nperseg, noverlap, detrend)
+    return freqs, _cross_output(c, rest, axis)
+
+
+def _matrix_input(name, x, detrend):
+    x = np.asarray(x)
+    if np.iscomplexobj(x):
+        raise NotImplementedError(f"{name}: complex input does not run on the device")
+    if not (detrend is False or (isinstance(detrend, str) and detrend == 'constant')):
+        raise NotImplementedError(f"{name}: detrend = {detrend!r} (only 'constant' and False run on the device)")
+    if x.ndim != 2 or x.size == 0:
+        raise ValueError(f"{name}: x must be (time, rois)")
+    return torch.from_numpy(np.array(x, dtype=np.float64, order="C")).to(device)
+
+
+def csd_matrix(x, fs=1.0, window='hann', nperseg=None, noverlap=None, detrend='constant', scaling='density'):
+    """The cross-spectral matrix of x (time, rois), rois <= 1024: (freqs, P) with P [F][rois][rois]
+    complex, P[f][i][j] = scipy.signal.csd(x[:, i], x[:, j], ...)[1][f] -- SciPy's broadcast form
+    csd(x[:, :, None], x[:, None, :], axis=0) without its time x rois x rois intermediate."""
+    freqs, p = sigchain.csd(_matrix_input("csd_matrix", x, detrend), None, fs, window, nperseg, noverlap, detrend,
+                            scaling)
+    return freqs, p.cpu().numpy()
+
+
+def coherence_matrix(x, fs=1.0, window='hann', nperseg=None, noverlap=None, detrend='constant'):
+    """The magnitude-squared coherence between the columns of x (time, rois): (freqs, C) with
+    C [F][rois][rois] real, symmetric, the spectral counterpart of the FC matrix."""
+    freqs, c = sigchain.coherence(_matrix_input("coherence_matrix", x, detrend), None, fs, window, nperseg, noverlap,
+                                  detrend)
+    return freqs, c.cpu().numpy()
 
 
 def kuramoto(sign):
