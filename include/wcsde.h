@@ -383,6 +383,40 @@ int wc_csd(int64_t C, int64_t T, const double* x, int nperseg, int noverlap,
            const double* window, int detrend, double scale, int mode, double* out,
            void* workspace, size_t ws_bytes, void* stream);
 
+/* scipy.signal.spectrogram(x, axis=0) of every column of a time-major x [T][C] fp64
+ * (wc_spectrogram.hip): wc_welch_psd's / wc_csd's segments, window, detrend and scale,
+ * S = (T - nperseg) / (nperseg - noverlap) + 1 segments and F = nperseg/2 + 1 bins,
+ * nothing averaged.  X is the DFT of the windowed (detrend 1: mean-free) segment;
+ * mode selects what is written of it:
+ *   WC_SPEC_PSD        out [S][F][C] real, |X|^2 scale, doubled at every bin but 0
+ *                      and (even nperseg) nperseg/2;
+ *   WC_SPEC_COMPLEX    out [S][F][C] complex, interleaved (re, im): X sqrt(scale), no
+ *                      doubling (SciPy's mode='stft' scaling); the imaginary part at
+ *                      bins 0 and (even nperseg) nperseg/2 is exactly 0;
+ *   WC_SPEC_MAGNITUDE  out [S][F][C] real, |X| sqrt(scale);
+ *   WC_SPEC_ANGLE      out [S][F][C] real, atan2(im, re) of X in [-pi, pi]; a bin
+ *                      that is exactly zero gives 0.
+ * The layout is segment-major (a transform workgroup holds neighbouring columns of a
+ * bin, which it writes contiguously); SciPy's [F][C][S] is the permuted view.
+ * 2 <= nperseg <= 4096 (larger: WC_EUNSUPPORTED), 0 <= noverlap < nperseg,
+ * T >= nperseg, 1 <= C <= 2^24, x and out below 2^62 bytes each; out must not alias x
+ * (over the mode's own size, S F C cells of 8 or 16 bytes); x, window, out 8-byte and
+ * the workspace 16-byte aligned.  Every argument is validated before any device work.
+ * The workspace holds the tables only (W_8192, the chirp padded to 16 entries and its
+ * spectrum [L], L = max(64, nextpow2(2 nperseg - 1))): (8192 + ceil(nperseg/16) 16 + L)
+ * 16 bytes, whatever C and T; the size function returns 0 for nperseg < 2 or > 4096.
+ * No atomics, nothing accumulated: a cell depends on its column's samples in its
+ * segment pair only (segments 2k and 2k + 1 share a transform), and the result is
+ * bit-identical for every C, every position of the column and from run to run. */
+#define WC_SPEC_PSD 0
+#define WC_SPEC_COMPLEX 1
+#define WC_SPEC_MAGNITUDE 2
+#define WC_SPEC_ANGLE 3
+size_t wc_spectrogram_workspace_size(int nperseg);
+int wc_spectrogram(int64_t C, int64_t T, const double* x, int nperseg, int noverlap,
+                   const double* window, int detrend, double scale, int mode, double* out,
+                   void* workspace, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,7 +1,7 @@
 """Device-side signal chain: BOLD + band-pass filtfilt + decimation, FC and
 goodness of fit, Kuramoto, Welch peak, band-limited amplitude envelopes, Welch
-spectra per column, cross spectra and coherence between columns -- thin
-wrappers over libwcsde.so.
+spectra per column, cross spectra and coherence between columns, spectrograms
+per column -- thin wrappers over libwcsde.so.
 
 References: simBOLD netwWilsonCowanPlastic.py:140-158; np.corrcoef
 whole_sweep_both.py:81; utils.get_all_metrics / kuramoto utils.py:34-50; Welch
@@ -474,6 +474,56 @@ def coherence(x, y=None, fs=1.0, window="hann", nperseg=None, noverlap=None, det
     real fp64 on the device: [F][C][C] between x's columns (y None), [F][C] =
     scipy.signal.coherence(x, y, axis=0) otherwise.  A column without power gives NaN, as SciPy."""
     return _csd("coherence", True, x, y, fs, window, nperseg, noverlap, detrend, "density", ws_bytes)
+
+
+SPEC_MODES = {"psd": 0, "complex": 1, "magnitude": 2, "angle": 3}  # WC_SPEC_*
+
+
+def spectrogram(x, fs=1.0, window=("tukey", 0.25), nperseg=None, noverlap=None, detrend="constant",
+                scaling="density", mode="psd"):
+    """scipy.signal.spectrogram(x, fs, window, nperseg, noverlap, detrend=detrend, scaling=scaling,
+    axis=0, mode=mode) of a device tensor x [T][C] or [T][B][N] fp64 (wc_spectrogram: one-sided,
+    2 <= nperseg <= 4096) -> (freqs, times, Sxx): freqs [F], F = nperseg // 2 + 1, and times [S],
+    the segments' centres, numpy arrays equal to SciPy's; Sxx a device tensor of SciPy's shape,
+    [F][C][S] or [F][B][N][S], float64 (mode "complex": complex128).
+
+    Sxx is a permuted view, without a copy, of the segment-major [S][F][C] buffer the kernel
+    writes (SciPy's own result is a non-contiguous view too): call .contiguous() where a consumer
+    needs the segments adjacent in memory.
+
+    window, nperseg, detrend and scaling are welch's, with SciPy's spectrogram defaults: a Tukey
+    (0.25) window, nperseg None -> 256 (an array window: its length), noverlap None -> nperseg // 8
+    of the nperseg in use (after a named window's nperseg > T is clamped to T with SciPy's
+    UserWarning).  mode: "psd", "complex" (the segments' spectra, SciPy's stft scaling),
+    "magnitude" or "angle" (in [-pi, pi]; an exactly zero bin gives 0).  "phase" is an unwrapping of
+    the angles that the device does not do (utils.spectrogram does it on the host):
+    NotImplementedError."""
+    if mode == "phase":
+        raise NotImplementedError("spectrogram: mode = 'phase' (unwrapped angles) does not run on the device; "
+                                  "utils.spectrogram unwraps the device's angles on the host")
+    if mode not in SPEC_MODES:
+        raise ValueError(f"unknown value for mode {mode}, must be one of {list(SPEC_MODES) + ['phase']}")
+    if x.dtype != torch.float64 or x.dim() < 2:
+        raise TypeError("spectrogram: x must be a [T][C] or [T][B][N] fp64 device tensor")
+    T = x.shape[0]
+    det, win, nperseg, nov, scale, freqs = _welch_args("spectrogram", T, x.device, fs, window, nperseg, noverlap,
+                                                       detrend, scaling)
+    if noverlap is None:
+        nov = nperseg // 8                        # of the clamped nperseg, as SciPy
+    step = nperseg - nov
+    times = np.arange(nperseg / 2, T - nperseg / 2 + 1, step) / float(fs)
+
+    L = _lib.lib()
+    x2 = x.reshape(T, -1).contiguous()
+    C = x2.shape[1]
+    F = nperseg // 2 + 1
+    S = (T - nperseg) // step + 1 if T >= nperseg else 0
+    ws_bytes = L.wc_spectrogram_workspace_size(nperseg) or 16  # 0: the call says why
+    out = torch.empty((S, F, C), dtype=torch.complex128 if mode == "complex" else torch.float64, device=x.device)
+    ws = torch.empty(ws_bytes // 8, dtype=torch.float64, device=x.device)
+    _lib.check(L.wc_spectrogram(C, T, _lib.ptr(x2), nperseg, nov, _lib.ptr(win), det, scale, SPEC_MODES[mode],
+                                _lib.ptr(out), _lib.ptr(ws), ws_bytes, _lib.stream_handle()), "wc_spectrogram")
+    return freqs, times, out.view((S, F) + tuple(x.shape[1:])).movedim(0, -1)
 
 
 def sim_bold(E_t, bold_downsamp=1000, neq=NEQ, bold_dt=0.04):

@@ -4,7 +4,8 @@ get_all_metrics, kuramoto and envelope run in libwcsde.so (wc_fc_metrics,
 wc_hilbert_phase / wc_hilbert_phase_long + wc_kuramoto, wc_filtfilt +
 wc_hilbert_envelope), and so does welch, a stand-in for the scipy.signal.welch
 that cortex_run.py:203-209 calls next to them (wc_welch_psd), with csd, coherence, csd_matrix and coherence_matrix for
-the coupling between regions per frequency (wc_csd); the small array helpers the reference defines next to
+the coupling between regions per frequency (wc_csd) and spectrogram for the spectra over time
+(wc_spectrogram); the small array helpers the reference defines next to
 them (flat_FC, new_metric, cohen_d, sub_weight, cortex_mat, scale_mat and the
 thal / sub / cortex index lists) are host numpy for callers that import them.
 Not mirrored: RSN_profile_FC and fill_missing (they cannot run upstream: the
@@ -114,6 +115,50 @@ def welch(x, fs=1.0, window='hann', nperseg=None, noverlap=None, nfft=None, detr
     freqs, psd = sigchain.welch(xd, fs, window, nperseg, noverlap, detrend, scaling)
     pxx = psd.cpu().numpy().reshape((psd.shape[0],) + rest)
     return freqs, np.moveaxis(pxx, 0, axis) if rest else pxx
+
+
+def spectrogram(x, fs=1.0, window=('tukey', .25), nperseg=None, noverlap=None, nfft=None, detrend='constant',
+                return_onesided=True, scaling='density', axis=-1, mode='psd'):
+    """scipy.signal.spectrogram with its parameter order and defaults, on the device
+    (wc_spectrogram), under welch's restrictions: real input, one-sided, no nfft padding, detrend
+    'constant' or False, 2 <= nperseg <= 4096.  numpy in, numpy (f, t, Sxx) out, shaped as SciPy's
+    (the frequencies where axis was, the segments last); anything else SciPy's spectrogram offers
+    raises NotImplementedError.  mode 'phase' is np.unwrap, on the host, of the device's angles
+    along the last axis, the segments: each bin's phase is continuous over time.  (SciPy 1.15
+    passes its adjusted data axis to np.unwrap, which is the frequency axis of its result; the
+    two agree up to multiples of 2 pi.)"""
+    modes = ['psd', 'complex', 'magnitude', 'angle', 'phase']
+    if mode not in modes:
+        raise ValueError(f'unknown value for mode {mode}, must be one of {modes}')
+    if nfft is not None:
+        named = isinstance(window, (str, tuple))
+        seg = int(nperseg) if nperseg is not None else (256 if named else len(window))
+        if named:
+            seg = min(seg, np.shape(x)[axis])  # SciPy clamps a named window's nperseg to the input
+        if int(nfft) != seg:
+            raise NotImplementedError("spectrogram: nfft other than nperseg (zero padding) does not run on the "
+                                      "device")
+    if not return_onesided:
+        raise NotImplementedError("spectrogram: return_onesided=False does not run on the device")
+    if not (detrend is False or (isinstance(detrend, str) and detrend == 'constant')):
+        raise NotImplementedError(f"spectrogram: detrend = {detrend!r} (only 'constant' and False run on the "
+                                  "device)")
+    x = np.asarray(x)
+    if np.iscomplexobj(x):
+        raise NotImplementedError("spectrogram: complex input x does not run on the device")
+    if x.ndim < 1 or x.size == 0:
+        raise ValueError("spectrogram: x must have at least one sample")
+    xt = np.moveaxis(x, axis, 0)
+    rest = xt.shape[1:]
+    xd = torch.as_tensor(np.ascontiguousarray(xt.reshape(xt.shape[0], -1), dtype=np.float64)).to(device)
+    freqs, times, sxx = sigchain.spectrogram(xd, fs, window, nperseg, noverlap, detrend, scaling,
+                                             'angle' if mode == 'phase' else mode)
+    sxx = sxx.cpu().numpy().reshape((sxx.shape[0],) + rest + (sxx.shape[-1],))
+    if mode == 'phase':
+        sxx = np.unwrap(sxx, axis=-1)
+    if rest:  # the segments are a new last axis: a negative data axis counts from one further back
+        sxx = np.moveaxis(sxx, 0, axis - 1 if axis < 0 else axis)
+    return freqs, times, sxx
 
 
 def _cross_input(name, x, y, window, nperseg, nfft, detrend, axis, return_onesided=True, average='mean'):
