@@ -417,6 +417,44 @@ int wc_spectrogram(int64_t C, int64_t T, const double* x, int nperseg, int nover
                    const double* window, int detrend, double scale, int mode, double* out,
                    void* workspace, size_t ws_bytes, void* stream);
 
+/* Phase and envelope connectivity between the columns of every simulation
+ * (wc_phaseconn.hip), from the unit phasors phasor [M][B][N][2] = (cos, sin) of
+ * wc_hilbert_phase / wc_hilbert_phase_long (B = 1, N = C for a plain [T][C] array;
+ * taken as given) and the envelopes amp [M][B][N] of wc_hilbert_envelope.  For
+ * columns i != j of one simulation, with u the phasors and a the envelopes,
+ *   c(t) = u_i.x u_j.x + u_i.y u_j.y
+ *   s(t) = u_i.y u_j.x - u_i.x u_j.y      (two rounded products and one subtraction,
+ *                                          never an FMA: identical columns give 0)
+ *   WC_CONN_PLV       sqrt((sum_t c)^2 + (sum_t s)^2) / M               diagonal 1
+ *   WC_CONN_PLI       |sum_t sign(s)| / M, sign(0) = 0                  diagonal 0
+ *   WC_CONN_WPLI      |sum_t a_i a_j s| / sum_t |a_i a_j s|             diagonal 0
+ *   WC_CONN_AEC_ORTH  (corr_t(a_i |s|, a_j) + corr_t(a_j |s|, a_i)) / 2 diagonal 0
+ * (corr: Pearson's coefficient; the envelope of one column orthogonal to the other's
+ * phase, Hipp et al. 2012, no logarithm, no absolute value).  A zero denominator
+ * gives NaN: wpli and aec_orth of two identical columns, aec_orth with a constant
+ * envelope.  measures is a non-empty set of the bits; out holds one [B][N][N] matrix
+ * per set bit, in ascending bit order, each exactly symmetric.  amp may be NULL
+ * exactly when neither WC_CONN_WPLI nor WC_CONN_AEC_ORTH is set.  (The plain
+ * amplitude-envelope correlation is wc_corrcoef of the envelopes.)
+ * B >= 1, 1 <= N <= 1024 (more: WC_EUNSUPPORTED), 2 <= M <= 524288 (more:
+ * WC_EUNSUPPORTED); out must not alias phasor or amp; phasor, amp, out 8-byte and the
+ * workspace 16-byte aligned.  Every argument is validated before any device work.
+ * The sums run over time blocks of 4096 samples and 32 x 32 column tiles; with
+ * nt = ceil(N / 32), nblk = ceil(M / 4096), the workspace holds the blocks' partial
+ * sums, B nt (nt + 1) / 2 nblk K 8192 bytes with K = 8 if an amplitude bit is set
+ * and 3 otherwise, plus B nblk N 16 bytes (rounded up to 16) for WC_CONN_AEC_ORTH;
+ * more is not used.  The size function returns 0 where the call would return
+ * neither WC_OK nor WC_EWORKSPACE.  No atomics: an entry depends on the samples of
+ * its own two columns, M and the measure only -- not on N, B, its position, the
+ * workspace size, the other measures asked for or the run. */
+#define WC_CONN_PLV 1
+#define WC_CONN_PLI 2
+#define WC_CONN_WPLI 4
+#define WC_CONN_AEC_ORTH 8
+size_t wc_phase_conn_workspace_size(int B, int N, int64_t M, int measures);
+int wc_phase_conn(int B, int N, int64_t M, const double* phasor, const double* amp, int measures,
+                  double* out, void* workspace, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

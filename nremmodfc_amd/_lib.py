@@ -89,6 +89,8 @@ _SIGNATURES = {
     "wc_csd": (c_int, [c_i64, c_i64, c_vp, c_int, c_int, c_vp, c_int, c_dbl, c_int, c_vp, c_vp, c_sz, c_vp]),
     "wc_spectrogram_workspace_size": (c_sz, [c_int]),
     "wc_spectrogram": (c_int, [c_i64, c_i64, c_vp, c_int, c_int, c_vp, c_int, c_dbl, c_int, c_vp, c_vp, c_sz, c_vp]),
+    "wc_phase_conn_workspace_size": (c_sz, [c_int, c_int, c_i64, c_int]),
+    "wc_phase_conn": (c_int, [c_int, c_int, c_i64, c_vp, c_vp, c_int, c_vp, c_vp, c_sz, c_vp]),
 }
 
 

@@ -1,7 +1,8 @@
 """Device-side signal chain: BOLD + band-pass filtfilt + decimation, FC and
 goodness of fit, Kuramoto, Welch peak, band-limited amplitude envelopes, Welch
 spectra per column, cross spectra and coherence between columns, spectrograms
-per column -- thin wrappers over libwcsde.so.
+per column, phase and envelope connectivity between columns -- thin wrappers
+over libwcsde.so.
 
 References: simBOLD netwWilsonCowanPlastic.py:140-158; np.corrcoef
 whole_sweep_both.py:81; utils.get_all_metrics / kuramoto utils.py:34-50; Welch
@@ -524,6 +525,120 @@ def spectrogram(x, fs=1.0, window=("tukey", 0.25), nperseg=None, noverlap=None, 
     _lib.check(L.wc_spectrogram(C, T, _lib.ptr(x2), nperseg, nov, _lib.ptr(win), det, scale, SPEC_MODES[mode],
                                 _lib.ptr(out), _lib.ptr(ws), ws_bytes, _lib.stream_handle()), "wc_spectrogram")
     return freqs, times, out.view((S, F) + tuple(x.shape[1:])).movedim(0, -1)
+
+
+CONN_BITS = {"plv": 1, "pli": 2, "wpli": 4, "aec_orth": 8}  # WC_CONN_*, the order of wc_phase_conn's out
+CONN_MEASURES = ("plv", "pli", "wpli", "aec", "aec_orth")
+
+
+def _conn_measures(name, measures):
+    """The requested measures as a tuple of known names, each once."""
+    names = (measures,) if isinstance(measures, str) else tuple(measures)
+    for m in names:
+        if m not in CONN_MEASURES:
+            raise ValueError(f"{name}: unknown measure {m!r}, must be one of {list(CONN_MEASURES)}")
+    if not names:
+        raise ValueError(f"{name}: no measure asked for, choose from {list(CONN_MEASURES)}")
+    return tuple(dict.fromkeys(names))
+
+
+AEC_GROUP = 48      # _aec_corrcoef: columns per group, two groups a wc_corrcoef call (its N <= 96 kernels)
+
+
+def _aec_corrcoef(amp):
+    """corrcoef of the envelopes amp [M][B][N] -> [B][N][N], of which only the entries i < j are
+    defined.  N <= 96: one corrcoef call.  Beyond, wc_corrcoef would change kernels (wc_fc_large.hip
+    takes the mean as one sum over time, wc_corr.hip from time-block sums) and an entry would differ
+    in its last bit from the same two columns' entry in a narrower call; so the columns go in groups
+    of AEC_GROUP and every pair of groups a <= b through a call of its own, always the N <= 96
+    kernels, where an entry depends on its two columns, M and B only."""
+    M, B, N = amp.shape
+    if N <= 2 * AEC_GROUP:
+        return corrcoef(amp, B, N)
+    fc = torch.empty((B, N, N), dtype=torch.float64, device=amp.device)
+    groups = [(g, min(g + AEC_GROUP, N)) for g in range(0, N, AEC_GROUP)]
+    for ka, (a0, a1) in enumerate(groups):
+        if a1 - a0 > 1:
+            fc[:, a0:a1, a0:a1] = corrcoef(amp[:, :, a0:a1].contiguous(), B, a1 - a0)
+        for b0, b1 in groups[ka + 1:]:
+            both = torch.cat((amp[:, :, a0:a1], amp[:, :, b0:b1]), dim=2)
+            fc[:, a0:a1, b0:b1] = corrcoef(both, B, both.shape[2])[:, :a1 - a0, a1 - a0:]
+    return fc
+
+
+def phase_connectivity_from(phasor, amp=None, measures=CONN_MEASURES, ws_bytes=None):
+    """Connectivity matrices from tensors the caller already holds: phasor [T][C][2] or
+    [T][B][N][2] fp64 (hilbert_phase's unit phasors) and, for "wpli", "aec" and "aec_orth", the
+    envelopes amp [T][C] or [T][B][N] fp64 (hilbert_envelope) -> a dict from measure name to a
+    [C][C] or [B][N][N] device tensor; pairs are formed within a simulation b only.
+
+    "plv", "pli", "wpli" and "aec_orth" come from wc_phase_conn (N <= 1024), "aec" from corrcoef of
+    the envelopes (N > 96: of every pair of 48-column groups, _aec_corrcoef): its entries i < j,
+    mirrored, with the defined diagonal, 1 (wc_corrcoef needs two columns: a single column gives
+    that diagonal alone).  Every matrix is exactly symmetric;
+    the diagonals are 1 (plv, aec) and 0.  A zero denominator gives NaN (wpli and aec_orth of two
+    identical columns, a constant envelope).  ws_bytes: workspace size (default and least: the
+    minimum); the result does not depend on it."""
+    names = _conn_measures("phase_connectivity_from", measures)
+    if not isinstance(phasor, torch.Tensor) or phasor.dtype != torch.float64 or phasor.dim() not in (3, 4) \
+            or phasor.shape[-1] != 2:
+        raise TypeError("phase_connectivity_from: phasor must be a [T][C][2] or [T][B][N][2] fp64 device tensor")
+    need_amp = any(m in ("wpli", "aec", "aec_orth") for m in names)
+    if need_amp and (not isinstance(amp, torch.Tensor) or amp.dtype != torch.float64
+                     or amp.shape != phasor.shape[:-1] or amp.device != phasor.device):
+        raise TypeError("phase_connectivity_from: wpli, aec and aec_orth need amp, an fp64 tensor of the "
+                        "phasors' [T][C] or [T][B][N] on their device")
+    M = phasor.shape[0]
+    B, N = (1, phasor.shape[1]) if phasor.dim() == 3 else (phasor.shape[1], phasor.shape[2])
+    shape = (N, N) if phasor.dim() == 3 else (B, N, N)
+    phasor = phasor.contiguous()
+    amp = amp.contiguous() if need_amp else None
+    res = {}
+    bits = sum(CONN_BITS[m] for m in names if m in CONN_BITS)
+    if bits:
+        L = _lib.lib()
+        need = L.wc_phase_conn_workspace_size(B, N, M, bits)
+        nbytes = max(need, ws_bytes or 0) or 16      # need == 0: the call says why
+        ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=phasor.device)
+        got = [m for m in CONN_BITS if CONN_BITS[m] & bits]  # ascending bit order
+        out = torch.empty((len(got), B, N, N), dtype=torch.float64, device=phasor.device)
+        _lib.check(L.wc_phase_conn(B, N, M, _lib.ptr(phasor), _lib.ptr(amp if bits & 12 else None), bits,
+                                   _lib.ptr(out), _lib.ptr(ws), nbytes, _lib.stream_handle()), "wc_phase_conn")
+        for k, m in enumerate(got):
+            res[m] = out[k].view(shape)
+    if "aec" in names:
+        if N > 1:
+            # wc_corrcoef keeps np.corrcoef's division order in either triangle (c / sd_i / sd_j against
+            # c / sd_j / sd_i: a last-bit difference) and its computed diagonal: the entries i < j are kept
+            # and mirrored, the diagonal is set
+            fc = _aec_corrcoef(amp.view(M, B, N))
+            upper = torch.ones((N, N), dtype=torch.bool, device=fc.device).triu(1)
+            aec = torch.where(upper, fc, fc.transpose(1, 2))
+            aec.diagonal(dim1=1, dim2=2).fill_(1.0)
+        else:
+            aec = torch.ones((B, 1, 1), dtype=torch.float64, device=phasor.device)
+        res["aec"] = aec.view(shape)
+    return {m: res[m] for m in names}
+
+
+def phase_connectivity(x, measures=CONN_MEASURES):
+    """Phase and envelope connectivity between the columns of a real, already band-limited device
+    tensor x [T][C] or [T][B][N] fp64 -> a dict from measure name to a [C][C] or [B][N][N] tensor:
+    "plv" phase-locking value, "pli" phase-lag index, "wpli" weighted phase-lag index, "aec"
+    amplitude-envelope correlation, "aec_orth" its pairwise orthogonalised form (Hipp et al. 2012,
+    no logarithm), all from z = scipy.signal.hilbert(x, axis=0): the phasors z / |z| through
+    hilbert_phase, the envelopes |z| (only where a measure needs them) through hilbert_envelope,
+    each with its own dispatch.  2 <= T <= 524288, N <= 1024; see phase_connectivity_from."""
+    names = _conn_measures("phase_connectivity", measures)
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.float64 or x.dim() not in (2, 3):
+        raise TypeError("phase_connectivity: x must be a [T][C] or [T][B][N] fp64 device tensor")
+    T = x.shape[0]
+    x2 = x.reshape(T, -1).contiguous()
+    ph = hilbert_phase(x2).view(tuple(x.shape) + (2,))
+    amp = None
+    if any(m in ("wpli", "aec", "aec_orth") for m in names):
+        amp = hilbert_envelope(x2).view(x.shape)
+    return phase_connectivity_from(ph, amp, names)
 
 
 def sim_bold(E_t, bold_downsamp=1000, neq=NEQ, bold_dt=0.04):

@@ -4,8 +4,9 @@ get_all_metrics, kuramoto and envelope run in libwcsde.so (wc_fc_metrics,
 wc_hilbert_phase / wc_hilbert_phase_long + wc_kuramoto, wc_filtfilt +
 wc_hilbert_envelope), and so does welch, a stand-in for the scipy.signal.welch
 that cortex_run.py:203-209 calls next to them (wc_welch_psd), with csd, coherence, csd_matrix and coherence_matrix for
-the coupling between regions per frequency (wc_csd) and spectrogram for the spectra over time
-(wc_spectrogram); the small array helpers the reference defines next to
+the coupling between regions per frequency (wc_csd), spectrogram for the spectra over time
+(wc_spectrogram) and connectivity for the coupling between regions in a band, from phases and
+envelopes (wc_phase_conn); the small array helpers the reference defines next to
 them (flat_FC, new_metric, cohen_d, sub_weight, cortex_mat, scale_mat and the
 thal / sub / cortex index lists) are host numpy for callers that import them.
 Not mirrored: RSN_profile_FC and fill_missing (they cannot run upstream: the
@@ -241,6 +242,31 @@ def coherence_matrix(x, fs=1.0, window='hann', nperseg=None, noverlap=None, detr
     freqs, c = sigchain.coherence(_matrix_input("coherence_matrix", x, detrend), None, fs, window, nperseg, noverlap,
                                   detrend)
     return freqs, c.cpu().numpy()
+
+
+def connectivity(series, dt=0.002, freqs=[8, 13], measures=("plv", "pli", "wpli", "aec", "aec_orth"),
+                 device="cuda"):
+    """Phase and envelope connectivity of series (time, rois) or (time, B, N) in a band: utils.envelope's
+    Bessel order-3 band-pass filtfilt over freqs (Hz, at sampling step dt; freqs=None: series is taken
+    as band-limited already), then, from the analytic signal along time, the matrices between the
+    columns of each simulation: "plv" phase-locking value, "pli" phase-lag index, "wpli" weighted
+    phase-lag index, "aec" amplitude-envelope correlation and "aec_orth" its pairwise
+    orthogonalised form (sigchain.phase_connectivity).  numpy in (float32 accepted), a dict of
+    numpy arrays (rois, rois) or (B, N, N) out.  time <= 524288 (with a band-pass: >= 22, the
+    order-6 filter's padlen is 21), N <= 1024."""
+    names = sigchain._conn_measures("connectivity", measures)
+    x = np.asarray(series)
+    if x.dtype.kind not in "fiub":
+        raise TypeError(f"connectivity: series must be real numbers, not {x.dtype}")
+    if x.ndim not in (2, 3) or x.size == 0:
+        raise ValueError("series must be (time, rois) or (time, B, N)")
+    if freqs is not None and len(freqs) != 2:
+        raise ValueError("freqs must be [fmin, fmax] or None")
+    xt = torch.from_numpy(np.array(x, dtype=np.float64, order="C")).to(device)
+    if freqs is not None:
+        (bb, ba), _ = sigchain.envelope_filters(float(dt), float(freqs[0]), float(freqs[1]), None)
+        xt = sigchain.filtfilt(bb, ba, xt)
+    return {m: v.cpu().numpy() for m, v in sigchain.phase_connectivity(xt, names).items()}
 
 
 def kuramoto(sign):
