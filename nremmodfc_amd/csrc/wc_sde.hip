@@ -81,6 +81,7 @@ struct KArgs {
     int zgen_b0, zgen_K;
     int64_t zgen_step0;
     int b0;  // first simulation of this launch (a launch may cover a range of the groups of 16)
+    uint32_t stagger;  // V_STAG: bit w set = wave w of the workgroup draws its normals before the coupling
 };
 
 // ---------------- A-operand (connectome) images ----------------
@@ -163,6 +164,44 @@ struct PkConsts {
     f2v a_ee, Pm, knoise, cIe, cIi, cI0, rE, rI, dtE, dtI, dtA, rhoE, cA;
 };
 
+// V_PKC: the same constants two per VGPR pair (12 registers instead of 26); each use names the
+// half it reads for BOTH cells through op_sel / op_sel_hi, so no instruction is added and every
+// rounding is the duplicated form's.
+struct PkB {
+    f2v eP;   // (a_ee, P - mu)
+    f2v cI;   // (cIe, cI0)
+    f2v nI;   // (knoise, cIi)
+    f2v r;    // (-rE, -rI)
+    f2v dt;   // (dtE, dtI)
+    f2v dA;   // (dtA, cA)
+};
+
+// ka[HA] * b + c as one v_pk_fma_f32, c = kc[HC] (HC = 0, 1), the vector kc (HC = -1) or 1.0
+// (HC = -2, kc unused).  Thin wrappers: the compiler folds a broadcast into op_sel only from an SGPR
+// or a splat built in the same block, and a loop-invariant splat is hoisted as a {c, c} pair.  Their
+// inputs are never the direct result of a transcendental or an MFMA (the hazard recogniser does
+// not look inside an asm block): every call site below feeds them state, constants, normals
+// (a v_pk_mul result) or a packed fma.
+template <int HA, int HC>
+__device__ __forceinline__ f2v pk_fma_k(f2v ka, f2v b, f2v kc) {
+    static_assert((HA == 0 || HA == 1) && HC >= -2 && HC <= 1, "half selectors");
+    f2v d;
+    if constexpr (HC == -2) {
+        if constexpr (HA == 0) asm("v_pk_fma_f32 %0, %1, %2, 1.0 op_sel_hi:[0,1,0]" : "=v"(d) : "v"(ka), "v"(b));
+        else asm("v_pk_fma_f32 %0, %1, %2, 1.0 op_sel:[1,0,0] op_sel_hi:[1,1,0]" : "=v"(d) : "v"(ka), "v"(b));
+    } else if constexpr (HC == -1) {
+        if constexpr (HA == 0) asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel_hi:[0,1,1]" : "=v"(d) : "v"(ka), "v"(b), "v"(kc));
+        else asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,0,0] op_sel_hi:[1,1,1]" : "=v"(d) : "v"(ka), "v"(b), "v"(kc));
+    } else if constexpr (HC == 0) {
+        if constexpr (HA == 0) asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel_hi:[0,1,0]" : "=v"(d) : "v"(ka), "v"(b), "v"(kc));
+        else asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,0,0] op_sel_hi:[1,1,0]" : "=v"(d) : "v"(ka), "v"(b), "v"(kc));
+    } else {
+        if constexpr (HA == 0) asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,0,1] op_sel_hi:[0,1,1]" : "=v"(d) : "v"(ka), "v"(b), "v"(kc));
+        else asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,0,1] op_sel_hi:[1,1,1]" : "=v"(d) : "v"(ka), "v"(b), "v"(kc));
+    }
+    return d;
+}
+
 // Two cells of the folded-constant fp32 update (wc:77-83; the scalar form is in wc_sde_kernel's
 // kFast branch) as packed fp32 math: v_pk_fma/mul/add_f32 carry two cells per instruction and
 // round exactly like their scalar forms, the transcendentals stay scalar.  Same operations in
@@ -190,28 +229,56 @@ struct PkConsts {
 // same value to within an fp32 rounding of a_ie.  AII0 (V_AII0): a_ii == 0 (the reference's
 // value, wc:25), so the inhibitory sigmoid's in * cIi term, exactly cI0 + 0, is dropped.
 #pragma clang fp contract(off)
-template <bool ES = false, bool LEAN = false, bool AII0 = false>
-__device__ __forceinline__ void cell_pair_f32(const PkConsts& k, f2v& e, f2v& in, f2v& ahi, f2v& alo, f2v cpl,
+// Each constant-carrying operation, in the duplicated (PkConsts) and the two-per-pair (PkB) form
+struct PkOps {
+    __device__ static __forceinline__ f2v xe(const PkConsts& k, f2v e0) { return __builtin_elementwise_fma(k.a_ee, e0, k.Pm); }
+    __device__ static __forceinline__ f2v xe(const PkB& k, f2v e0) { return pk_fma_k<0, 1>(k.eP, e0, k.eP); }
+    __device__ static __forceinline__ f2v xz(const PkConsts& k, f2v z, f2v x) { return __builtin_elementwise_fma(k.knoise, z, x); }
+    __device__ static __forceinline__ f2v xz(const PkB& k, f2v z, f2v x) { return pk_fma_k<0, -1>(k.nI, z, x); }
+    template <bool AII0> __device__ static __forceinline__ f2v ti(const PkConsts& k, f2v e0, f2v in0) {
+        return AII0 ? __builtin_elementwise_fma(e0, k.cIe, k.cI0)
+                    : __builtin_elementwise_fma(e0, k.cIe, __builtin_elementwise_fma(in0, k.cIi, k.cI0));
+    }
+    template <bool AII0> __device__ static __forceinline__ f2v ti(const PkB& k, f2v e0, f2v in0) {
+        if constexpr (AII0) return pk_fma_k<0, 1>(k.cI, e0, k.cI);
+        else return pk_fma_k<0, -1>(k.cI, e0, pk_fma_k<1, 1>(k.nI, in0, k.cI));
+    }
+    __device__ static __forceinline__ f2v inc(const PkConsts& k, f2v e0) { return __builtin_elementwise_fma(e0, k.dtA, k.cA); }
+    __device__ static __forceinline__ f2v inc(const PkB& k, f2v e0) { return pk_fma_k<0, 1>(k.dA, e0, k.dA); }
+    // 1 - rE e0, 1 - rI in0
+    __device__ static __forceinline__ f2v re(const PkConsts& k, f2v e0) { return __builtin_elementwise_fma(-k.rE, e0, f2v{1.0f, 1.0f}); }
+    __device__ static __forceinline__ f2v re(const PkB& k, f2v e0) { return pk_fma_k<0, -2>(k.r, e0, k.r); }
+    __device__ static __forceinline__ f2v ri(const PkConsts& k, f2v in0) { return __builtin_elementwise_fma(-k.rI, in0, f2v{1.0f, 1.0f}); }
+    __device__ static __forceinline__ f2v ri(const PkB& k, f2v in0) { return pk_fma_k<1, -2>(k.r, in0, k.r); }
+    // v + dt d
+    __device__ static __forceinline__ f2v ste(const PkConsts& k, f2v d, f2v e0) { return __builtin_elementwise_fma(k.dtE, d, e0); }
+    __device__ static __forceinline__ f2v ste(const PkB& k, f2v d, f2v e0) { return pk_fma_k<0, -1>(k.dt, d, e0); }
+    __device__ static __forceinline__ f2v sti(const PkConsts& k, f2v d, f2v in0) { return __builtin_elementwise_fma(k.dtI, d, in0); }
+    __device__ static __forceinline__ f2v sti(const PkB& k, f2v d, f2v in0) { return pk_fma_k<1, -1>(k.dt, d, in0); }
+};
+
+template <bool ES = false, bool LEAN = false, bool AII0 = false, typename K = PkConsts>
+__device__ __forceinline__ void cell_pair_f32(const K& k, f2v& e, f2v& in, f2v& ahi, f2v& alo, f2v cpl,
                                               f2v G, f2v sl, f2v z) {
     const f2v e0 = e, in0 = in;
-    f2v x = __builtin_elementwise_fma(k.a_ee, e0, k.Pm);
+    f2v x = PkOps::xe(k, e0);
     x = __builtin_elementwise_fma(LEAN ? -(ahi + alo) : -ahi, in0, x);
     x = __builtin_elementwise_fma(G, cpl, x);
-    x = __builtin_elementwise_fma(k.knoise, z, x);
+    x = PkOps::xz(k, z, x);
     const f2v te = x * sl;
     const f2v ex = {__builtin_amdgcn_exp2f(te.x), __builtin_amdgcn_exp2f(te.y)};
     const f2v one = {1.0f, 1.0f};
     constexpr float kS = ES ? 0x1p-10f : 1.0f;
     const f2v de = ES ? __builtin_elementwise_fma(ex, f2v{kS, kS}, f2v{kS, kS}) : one + ex;
     const f2v SE = {__builtin_amdgcn_rcpf(de.x), __builtin_amdgcn_rcpf(de.y)};
-    const f2v ti = AII0 ? __builtin_elementwise_fma(e0, k.cIe, k.cI0)
-                        : __builtin_elementwise_fma(e0, k.cIe, __builtin_elementwise_fma(in0, k.cIi, k.cI0));
+    const f2v ti = PkOps::template ti<AII0>(k, e0, in0);
     const f2v di = 1.0f + f2v{__builtin_amdgcn_exp2f(ti.x), __builtin_amdgcn_exp2f(ti.y)};
     const f2v SI = {__builtin_amdgcn_rcpf(di.x), __builtin_amdgcn_rcpf(di.y)};
     // (a_ie first: e0 and in0 are last read by their own updates, which can then write in place)
 #if WC_INC2
-    const f2v inc = in0 * __builtin_elementwise_fma(e0, k.dtA, k.cA);
+    const f2v inc = in0 * PkOps::inc(k, e0);
 #else
+    static_assert(std::is_same_v<K, PkConsts>, "V_PKC packs the WC_INC2 constants only");
     const f2v tA = in0 * k.dtA;
     const f2v inc = __builtin_elementwise_fma(e0, tA, -k.rhoE * tA);
 #endif
@@ -224,8 +291,8 @@ __device__ __forceinline__ void cell_pair_f32(const PkConsts& k, f2v& e, f2v& in
         ahi = s;
     }
     // (ES: SE and e0 both carry 2^10, rE 2^-10: the same roundings times 2^10)
-    e = __builtin_elementwise_fma(k.dtE, __builtin_elementwise_fma(__builtin_elementwise_fma(-k.rE, e0, one), SE, -e0), e0);
-    in = __builtin_elementwise_fma(k.dtI, __builtin_elementwise_fma(__builtin_elementwise_fma(-k.rI, in0, one), SI, -in0), in0);
+    e = PkOps::ste(k, __builtin_elementwise_fma(PkOps::re(k, e0), SE, -e0), e0);
+    in = PkOps::sti(k, __builtin_elementwise_fma(PkOps::ri(k, in0), SI, -in0), in0);
 }
 
 #pragma clang fp contract(on)
@@ -258,6 +325,11 @@ enum : int {
     V_ZPAIR = 524288, // SG = 2, V_ZMEM, one workgroup per CU: workgroups < zgen_b0 integrate two groups,
                       // the others one group while their second group's waves draw the next block's
                       // normals, one step's share per step between the workgroup's barriers
+    V_PKC = 2097152,  // packed fp32 update: the wave-uniform constants two per VGPR pair, the half chosen by
+                      // op_sel in each instruction (PkB: 12 registers instead of 26, the same instructions)
+    V_STAG = 4194304, // wave roles: a wave whose bit of KArgs::stagger is set draws the step's normals right
+                      // after the barrier, before its coupling phase, so that it issues VALU while the other
+                      // waves of its SIMD read LDS and run MFMAs (the same operations per cell: the same bits)
 };
 
 constexpr bool kFragRegs_(int var) { return (var & V_FRAG_REGS) != 0; }
@@ -300,6 +372,11 @@ __global__ void __launch_bounds__(NW * 64 * SG, MINW) wc_sde_kernel(const KArgs 
     static_assert(!kHalf || (kZMem && kHf && !kHf3), "V_HALF2: the fp16x3 packed path with precomputed normals");
     constexpr bool kZPair = (VAR & V_ZPAIR) != 0;
     static_assert(!kZPair || (kZMem && SG == 2 && NW > 1 && !kHalf), "V_ZPAIR: two groups, normals from zbuf");
+    constexpr bool kPkc = (VAR & V_PKC) != 0;
+    static_assert(!kPkc || (kFast && kPk), "V_PKC: the packed fp32 update");
+    constexpr bool kStag = (VAR & V_STAG) != 0;
+    static_assert(!kStag || (kFast && kPk && kRng && !kZMem && !kZFirst && !kMix && NW > 1),
+                  "V_STAG: the packed fp32 update drawing its own normals, several waves per workgroup");
     constexpr float kEsc = kEs ? 1024.0f : 1.0f, kEinv = kEs ? 0x1p-10f : 1.0f;
     // VALU slots after each MFMA in the interleaved schedule (0: compiler's own order)
     constexpr int kIlv = !(kZFirst && kBf && kMfma) ? 0 : (VAR & V_ILV) ? 6 : (VAR & V_ILV2) ? 2 : 0;
@@ -541,14 +618,24 @@ __global__ void __launch_bounds__(NW * 64 * SG, MINW) wc_sde_kernel(const KArgs 
         asm volatile("" : "+v"(rI), "+v"(mu), "+v"(slI), "+v"(sqdtD), "+v"(dt));
         asm volatile("" : "+v"(tauE), "+v"(tauI), "+v"(tau_ip));
     }
-    PkConsts pk{};
-    if constexpr (kFast && kPk) {
+    PkConsts pkd{};
+    PkB pkb{};
+    if constexpr (kPkc) {
+        // (-rE, -rI negated here; kEs scalings as below)
+        pkb = PkB{f2v{(float)a_ee * kEinv, Pm}, f2v{cIe * kEinv, cI0}, f2v{knoise, cIi},
+                  f2v{-((float)rE * kEinv), -(float)rI}, f2v{(float)dtE, (float)dtI},
+                  f2v{(float)dtA * kEinv, (float)(-a.rhoE * a.dtSim / a.tau_ip)}};
+    } else if constexpr (kFast && kPk) {
         auto bc = [](float v) { return f2v{v, v}; };
         // (kEs: E-side constants carry 2^-10, rhoE 2^10, all exact)
-        pk = PkConsts{bc((float)a_ee * kEinv), bc(Pm), bc(knoise), bc(cIe * kEinv), bc(cIi), bc(cI0),
-                      bc((float)rE * kEinv), bc((float)rI), bc((float)dtE), bc((float)dtI),
-                      bc((float)dtA * kEinv), bc((float)rhoE * kEsc), bc((float)(-a.rhoE * a.dtSim / a.tau_ip))};
+        pkd = PkConsts{bc((float)a_ee * kEinv), bc(Pm), bc(knoise), bc(cIe * kEinv), bc(cIi), bc(cI0),
+                       bc((float)rE * kEinv), bc((float)rI), bc((float)dtE), bc((float)dtI),
+                       bc((float)dtA * kEinv), bc((float)rhoE * kEsc), bc((float)(-a.rhoE * a.dtSim / a.tau_ip))};
     }
+    const auto& pk = *[&] {
+        if constexpr (kPkc) return &pkb;
+        else return &pkd;
+    }();
     const size_t BN = (size_t)a.B * N;
     const int rec_every = (int)a.rec_every;
     int rec_cnt = 0, rec_row = 0;
@@ -571,6 +658,12 @@ __global__ void __launch_bounds__(NW * 64 * SG, MINW) wc_sde_kernel(const KArgs 
 #pragma unroll
             for (int u = 0; u < OT; ++u) zq[d][u] = zload(min(d, a.nsteps - 1), u);
     }
+    // V_STAG: this wave's role, wave-uniform and fixed for the launch; bit = the wave's slot in the workgroup
+    // (role B: the normals of all its tiles drawn before the coupling phase and held across it, 4
+    // VGPRs per tile; role A: drawn after it.  One step loop with a scalar branch at both places:
+    // one loop per role spilled to scratch)
+    bool role_b = false;
+    if constexpr (kStag) role_b = __builtin_amdgcn_readfirstlane((int)((a.stagger >> (threadIdx.x >> 6)) & 1u)) != 0;
     // one Euler step; ZS = the V_ZMEM prefetch slot of step s (s % kZD: a compile-time index, so the
     // in-flight normals are never moved between registers -- a move would wait for every older load)
     auto step_body = [&](const int s, auto zslot) {
@@ -684,6 +777,15 @@ __global__ void __launch_bounds__(NW * 64 * SG, MINW) wc_sde_kernel(const KArgs 
 #pragma unroll
             for (int u = 0; u < OT; ++u) quad_normals_raw(gstep, (uint32_t)(4 * TL(u) + g), key, zz[u]);
         }
+        // V_STAG, role B: the update's own calls with the same arguments, issued while the role-A
+        // waves of this SIMD are in their coupling phase
+        f2v zh[kStag ? OT : 1][2];
+        if constexpr (kStag) {
+            if (role_b) {
+#pragma unroll
+                for (int u = 0; u < OT; ++u) quad_normals_pk(gstep, (uint32_t)(4 * TL(u) + g), key, zh[u]);
+            }
+        }
         if constexpr (kMfma && kBf) {
             const bf16x8* l16 = reinterpret_cast<const bf16x8*>(smem);
             const bf16x8* xb = xb16 + buf * NC * PS * 64;
@@ -762,6 +864,14 @@ __global__ void __launch_bounds__(NW * 64 * SG, MINW) wc_sde_kernel(const KArgs 
                 __builtin_amdgcn_sched_group_barrier(0x002, kIlv, 0);
             }
         }
+        // V_STAG, role A: the same draws here, after the coupling, for all its tiles at once
+        // (independent Philox chains side by side, as in role B)
+        if constexpr (kStag) {
+            if (!role_b) {
+#pragma unroll
+                for (int u = 0; u < OT; ++u) quad_normals_pk(gstep, (uint32_t)(4 * TL(u) + g), key, zh[u]);
+            }
+        }
         // ---- elementwise update (wc:77-83), noise drawn inside the E sigmoid ----
 #pragma unroll
         for (int u = 0; u < OT; ++u) {
@@ -793,7 +903,12 @@ __global__ void __launch_bounds__(NW * 64 * SG, MINW) wc_sde_kernel(const KArgs 
                     zp[0] = f2v{zz[u][0], zz[u][1]};
                     zp[1] = f2v{zz[u][2], zz[u][3]};
                 } else if constexpr (kRng) {
-                    quad_normals_pk(gstep, (uint32_t)(4 * TL(u) + g), key, zp);
+                    if constexpr (kStag) {
+                        zp[0] = zh[u][0];
+                        zp[1] = zh[u][1];
+                    } else {
+                        quad_normals_pk(gstep, (uint32_t)(4 * TL(u) + g), key, zp);
+                    }
                 }
 #pragma unroll
                 for (int h = 0; h < 2; ++h) {
@@ -1174,9 +1289,24 @@ int launch_zmem(const KArgs& ka, const double* sc, void* ws, hipStream_t st, int
 #ifndef WC_SG2
 #define WC_SG2 1  // CUs < groups <= 2 CUs: two six-wave groups per workgroup (0: one group per workgroup)
 #endif
+// V_STAG role mask of the large-batch kernels (four or five groups of three waves per workgroup): bit w
+// = wave slot w draws its normals first.  Waves are placed round-robin on the four SIMDs (masks that
+// give a SIMD one role only, 0x5555 or 0x3333, time like all-A), so SIMD s holds waves s, s + 4,
+// s + 8, s + 12.  Default: the second of them (waves 4..7) in role B, the others in role A; measured
+// 50.4 ms per C3 launch against 53.3 all-A, 53.0 all-B, 51.0 for 0x0F0F and 54.2 for its inverse
+// 0x70F0 (a mask that puts the last group, waves 12..14, in role B is slower than no stagger);
+// profiles/stagger/masks.log.  WCSDE_STAGGER=<hex>, read per call, overrides it (0: all role A);
+// the mask changes timing only, never results.
+constexpr uint32_t kStaggerDefault = 0x00F0u;
+uint32_t stagger_mask() {
+    const char* env = getenv("WCSDE_STAGGER");
+    return env && env[0] ? (uint32_t)strtoul(env, nullptr, 16) : kStaggerDefault;
+}
+
 template <int X>
 int launch_f32_nt6(const KArgs& ka, const double* sc, void* ws, hipStream_t st) {
     constexpr int V = V_F16X3 | V_KAHAN_A | X;
+    constexpr int VS = V | V_PKC | V_STAG;  // four and five groups per workgroup
     const int groups = (ka.B + kSims - 1) / kSims;
     const int cus = cu_count();
     if (groups <= 2 * cus) {
@@ -1209,8 +1339,8 @@ int launch_f32_nt6(const KArgs& ka, const double* sc, void* ws, hipStream_t st) 
 #else
         case 3: return rec2 ? launch_v<float, 6, 3, V2, 1, 3>(ka, sc, ws, st) : launch_v<float, 6, 3, V, 1, 3>(ka, sc, ws, st);
 #endif
-        case 4: return rec2 ? launch_v<float, 6, 3, V2, 1, 4>(ka, sc, ws, st) : launch_v<float, 6, 3, V, 1, 4>(ka, sc, ws, st);
-        default: return rec2 ? launch_v<float, 6, 3, V2, 1, 5>(ka, sc, ws, st) : launch_v<float, 6, 3, V, 1, 5>(ka, sc, ws, st);
+        case 4: return rec2 ? launch_v<float, 6, 3, VS | V_REC2, 1, 4>(ka, sc, ws, st) : launch_v<float, 6, 3, VS, 1, 4>(ka, sc, ws, st);
+        default: return rec2 ? launch_v<float, 6, 3, VS | V_REC2, 1, 5>(ka, sc, ws, st) : launch_v<float, 6, 3, VS, 1, 5>(ka, sc, ws, st);
     }
 }
 
@@ -1343,6 +1473,9 @@ int launch_diag(int variant, const KArgs& ka, const double* sc, void* ws, hipStr
         case 56: return launch_v<float, 6, 4, V_F16X3 | V_KAHAN_A | V_AII0 | V_MIX, 1, 3>(ka, sc, ws, st);
         // the C3 product configuration (= 41, time-major records as the bench) with the >= 24-bit coupling
         case 58: return launch_v<float, 6, 3, V_F16X6 | V_KAHAN_A | V_AII0, 1, 5>(ka, sc, ws, st);
+        // 41 with its constants two per VGPR pair; the same with wave roles (the product: WCSDE_STAGGER picks the mask)
+        case 60: return launch_v<float, 6, 3, V_F16X3 | V_KAHAN_A | V_AII0 | V_PKC, 1, 5>(ka, sc, ws, st);
+        case 61: return launch_v<float, 6, 3, V_F16X3 | V_KAHAN_A | V_AII0 | V_PKC | V_STAG, 1, 5>(ka, sc, ws, st);
         default: return wc_set_err(WC_EINVAL, "unknown diagnostic variant");
     }
 }
@@ -1374,6 +1507,7 @@ int make_args(KArgs& ka, const wc_params* p, int precision, int B, int N, const 
     ka.zbuf = nullptr;
     ka.zBp = 0;
     ka.b0 = 0;
+    ka.stagger = stagger_mask();
     if (precision == WC_F32 && zmem_eligible_shape(B, N) && ws_bytes >= zmem_offset(N) + 2 * zmem_block_bytes(B))
         ka.zbuf = reinterpret_cast<const float4*>(static_cast<char*>(workspace) + zmem_offset(N));
     return WC_OK;
