@@ -28,123 +28,21 @@
 // N, i.e. G neighbouring (n2, c) or (k1, c) items, whose points are G * 16
 // contiguous bytes in memory.  The sub-FFT is an in-place Stockham (every read of a
 // stage, barrier, every write, barrier), radix 4 with a leading radix-2 stage for
-// odd log2 N, twiddles from a 768-entry table of W_1024 in LDS; the inter-step
+// odd log2 N (wc_bluestein.h's stages, shared with the Welch family and inlined here),
+// twiddles from a 768-entry table of W_1024 in LDS; the inter-step
 // twiddles are sincospi of the exact fraction (n2 k1 < L needs no reduction).
 // No atomics, and a column's arithmetic does not depend on the tile it is in: the
 // result is bit-identical for every workspace size and every C.
-#include <hip/hip_runtime.h>
-#include <math.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <algorithm>
-#include "wc_common.h"
+#define WC_BLUESTEIN_FFT_ONLY
+#include "wc_bluestein.h"
 
 namespace {
 
-typedef double d2 __attribute__((ext_vector_type(2)));  // (re, im)
-
 constexpr int64_t kMaxM = 524288;  // L = 2^20 = L1 L2 with L1 = L2 = 1024
 constexpr int kMinLogL = 15;
-constexpr int kThreads = 512;
 constexpr int kPts = 4096;         // points per workgroup
 constexpr int kTwN = 1024;         // sub-FFT twiddle base: T[j] = exp(-2 pi i j / 1024)
-constexpr int kTwLds = 768;        // radix 4 reads j = r k 1024 / (4 P) < 768
 constexpr int kEpt = kPts / kThreads;  // points per thread on load / store
-
-__device__ __forceinline__ d2 cmul(d2 a, d2 w) {
-    return d2{__builtin_fma(a.x, w.x, -a.y * w.y), __builtin_fma(a.x, w.y, a.y * w.x)};
-}
-__device__ __forceinline__ d2 cconj(d2 a) { return d2{a.x, -a.y}; }
-
-// T[j] = exp(-2 pi i j / 1024), j < 1024
-__global__ void hl_twiddle_kernel(d2* T) {
-    const int j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= kTwN) return;
-    double s, c;
-    sincospi(2.0 * j / kTwN, &s, &c);
-    T[j] = d2{c, -s};
-}
-
-// w[k] = exp(-i pi k^2 / M): k^2 mod 2 M in integers (k < 2^19), then sincospi
-__global__ void hl_chirp_kernel(int64_t M, d2* w) {
-    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= M) return;
-    const int64_t r = (k * k) % (2 * M);
-    double s, c;
-    sincospi((double)r / (double)M, &s, &c);
-    w[k] = d2{c, -s};
-}
-
-// ---- forward FFT of the workgroup's G sub-FFTs of length N in LDS (item g at z + g (N + 1)) ----
-template <int N>
-__device__ __forceinline__ void r2_stage(d2* z, int tid) {  // first stage, P = 1: no twiddles
-    constexpr int S = N / 2, NP = N + 1, NB = kPts / 2 / kThreads;
-    d2 u[NB][2];
-#pragma unroll
-    for (int j = 0; j < NB; ++j) {
-        const int bf = tid + kThreads * j, g = bf / S, i = bf % S;
-        u[j][0] = z[g * NP + i];
-        u[j][1] = z[g * NP + i + S];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < NB; ++j) {
-        const int bf = tid + kThreads * j, g = bf / S, i = bf % S;
-        z[g * NP + 2 * i] = u[j][0] + u[j][1];
-        z[g * NP + 2 * i + 1] = u[j][0] - u[j][1];
-    }
-    __syncthreads();
-}
-
-// one radix-4 Stockham stage (P = product of the previous radices), as wc_welch.hip's
-template <int N, int P>
-__device__ __forceinline__ void r4_stage(d2* z, const d2* T, int tid) {
-    constexpr int S = N / 4, NP = N + 1, NB = kPts / 4 / kThreads;
-    d2 u[NB][4];
-#pragma unroll
-    for (int j = 0; j < NB; ++j) {
-        const int bf = tid + kThreads * j, g = bf / S, i = bf % S, k = i % P;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) u[j][r] = z[g * NP + i + r * S];
-        if constexpr (P > 1) {
-#pragma unroll
-            for (int r = 1; r < 4; ++r) u[j][r] = cmul(u[j][r], T[r * k * (kTwN / (4 * P))]);
-        }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < NB; ++j) {
-        const int bf = tid + kThreads * j, g = bf / S, i = bf % S, k = i % P;
-        const d2 a = u[j][0] + u[j][2], b = u[j][0] - u[j][2];
-        const d2 c = u[j][1] + u[j][3], d = u[j][1] - u[j][3];
-        d2* o = z + g * NP + (i - k) * 4 + k;
-        o[0] = a + c;
-        o[P] = d2{b.x + d.y, b.y - d.x};  // b - i d
-        o[2 * P] = a - c;
-        o[3 * P] = d2{b.x - d.y, b.y + d.x};  // b + i d
-    }
-    __syncthreads();
-}
-
-template <int N, int P>
-__device__ __forceinline__ void r4_stages(d2* z, const d2* T, int tid) {
-    if constexpr (P < N) {
-        r4_stage<N, P>(z, T, tid);
-        r4_stages<N, P * 4>(z, T, tid);
-    }
-}
-
-// every point of z written and a barrier passed before the call; ends with a barrier
-template <int LOGN>
-__device__ __forceinline__ void fft_lds(d2* z, const d2* T, int tid) {
-    constexpr int N = 1 << LOGN;
-    if constexpr (LOGN & 1) {
-        r2_stage<N>(z, tid);
-        r4_stages<N, 2>(z, T, tid);
-    } else {
-        r4_stages<N, 1>(z, T, tid);
-    }
-}
 
 struct HlArgs {
     int64_t C, M, c0;  // columns of x, samples, first column of the tile
@@ -202,7 +100,7 @@ __global__ void __launch_bounds__(kThreads) hl_col_kernel(const HlArgs a) {
     __syncthreads();
     constexpr bool kLast = MODE == kColLast || MODE == kColLastEnv;
     if constexpr (MODE == kColMid || kLast) {
-        fft_lds<LOGN>(z, T, tid);  // F = conj(c) L, c = the circular convolution
+        fft_lds<LOGN, kPts, kTwN>(z, T, tid);  // F = conj(c) L, c = the circular convolution
         const double sc = 1.0 / (double)a.L;
 #pragma unroll
         for (int j = 0; j < kEpt; ++j) {
@@ -228,7 +126,7 @@ __global__ void __launch_bounds__(kThreads) hl_col_kernel(const HlArgs a) {
         if constexpr (kLast) return;
         __syncthreads();
     }
-    fft_lds<LOGN>(z, T, tid);
+    fft_lds<LOGN, kPts, kTwN>(z, T, tid);
 #pragma unroll
     for (int j = 0; j < kEpt; ++j) {
         const int e = e0 + ES * j;
@@ -259,7 +157,7 @@ __global__ void __launch_bounds__(kThreads) hl_row_kernel(const HlArgs a) {
         zg[e] = a.src[(row + e) * a.tc + c];
     }
     __syncthreads();
-    fft_lds<LOGN>(z, T, tid);
+    fft_lds<LOGN, kPts, kTwN>(z, T, tid);
     if constexpr (!CONV) {  // the chirp spectrum (tc = 1)
 #pragma unroll
         for (int j = 0; j < kEpt; ++j) {
@@ -273,7 +171,7 @@ __global__ void __launch_bounds__(kThreads) hl_row_kernel(const HlArgs a) {
             zg[e] = cconj(cmul(zg[e], a.Bf[row + e]));
         }
         __syncthreads();
-        fft_lds<LOGN>(z, T, tid);
+        fft_lds<LOGN, kPts, kTwN>(z, T, tid);
 #pragma unroll
         for (int j = 0; j < kEpt; ++j) {
             const int e = e0 + ES * j;
@@ -368,8 +266,8 @@ static int hl_run(const char* who, bool envelope, int64_t C, int64_t M, const do
     d2* buf0 = Bf + L;
     const int64_t tcmax = (int64_t)std::min<size_t>((ws_bytes - tab) / per_col, (size_t)std::min<int64_t>(C, 1 << 20));
 
-    hipLaunchKernelGGL(hl_twiddle_kernel, dim3(kTwN / 256), dim3(256), 0, st, T);
-    hipLaunchKernelGGL(hl_chirp_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, st, M, w);
+    hipLaunchKernelGGL(bs_twiddle_kernel<kTwN>, dim3(kTwN / 256), dim3(256), 0, st, T);
+    hipLaunchKernelGGL(bs_chirp_kernel<int64_t>, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, st, M, w);
     HlArgs a{C, M, 0, 1, (int)L, 1 << log2, x, out, T, w, Bf, nullptr, buf0};
     hipError_t e = col_pass<kColChirp>(log1, a, st);
     a.src = buf0;

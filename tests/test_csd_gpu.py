@@ -11,13 +11,13 @@ dC <= eps (2 sqrt(r_i r_j) + r_i + r_j); on this signal r reaches about 2e8 in S
 flat bound would mean nothing.  Also 0 <= C <= 1 + 1e-12 and the diagonal within 1e-15 of 1.
 Every case prints its measured maximum in those units as a `TOL csd-... dev=` line.
 
-Measured on MI355X (370 printed figures; none reaches a tenth of its bound):
+Measured on MI355X (380 printed figures; none reaches a tenth of its bound):
   cross spectrum, worst over noverlap and segment count per nperseg, C = 7:  2: 2.8e-16   3: 9.6e-15   5: 3.3e-14
-    8: 8.5e-15   15: 6.8e-15   16: 6.3e-15   64: 5.5e-15   400: 1.5e-15   1000: 8.6e-16   1025: 8.2e-16   2049: 1.2e-15
-    4096: 5.4e-16  (the largest at nperseg = 5, as in the PSD tests: the detrended segment of an offset column
+    8: 8.5e-15   15: 6.8e-15   16: 6.3e-15   64: 5.5e-15   100: 2.5e-15   200: 3.9e-15   400: 1.5e-15   1000: 8.6e-16
+    1025: 8.2e-16   2049: 1.2e-15   4096: 5.4e-16  (the largest at nperseg = 5, as in the PSD tests: the detrended segment of an offset column
     is 1e-3 of its mean)
   coherence, the same cases:  2: 5.6e-16   3: 4.1e-15   5: 1.7e-14   8: 2.7e-15   15: 5.0e-15   16: 5.5e-15
-    64: 3.1e-15   400: 4.4e-16   1000: 1.8e-16   1025: 2.2e-16   2049: 3.5e-16   4096: 2.2e-16
+    64: 3.1e-15   100: 1.2e-15   200: 1.0e-15   400: 4.4e-16   1000: 1.8e-16   1025: 2.2e-16   2049: 3.5e-16   4096: 2.2e-16
   C = 1 / 2 / 33 / 90 / 130, cross spectrum:  nperseg 15: 8.0e-16 / 4.6e-16 / 3.1e-15 / 4.7e-15 / 5.8e-15
     1000: 4.7e-16 / 1.5e-16 / 4.9e-16 / 6.7e-16 / 7.6e-16;  coherence:  15: 0 / 2.2e-16 / 1.7e-15 / 2.6e-15 / 2.7e-15
     1000: 0 / 2.3e-17 / 6.8e-16 / 8.9e-16 / 1.0e-15
@@ -45,7 +45,7 @@ pytestmark = pytest.mark.gpu
 CSD_BOUND = 2e-12
 COH_BOUND = 8e-12
 PSD_BOUND = 1e-12
-NPERSEG = [2, 3, 5, 8, 15, 16, 64, 400, 1000, 1025, 2049, 4096]
+NPERSEG = [2, 3, 5, 8, 15, 16, 64, 100, 200, 400, 1000, 1025, 2049, 4096]
 
 
 def make_signal(M, C):

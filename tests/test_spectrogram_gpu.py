@@ -16,6 +16,7 @@ Measured on MI355X (the deviations above; none of the printed cases above 4.8e-1
 the bound; per case in docs/CHANGELOG.md):
   worst over noverlap and T per nperseg, C = 7, psd / complex:  2: 1.2e-16 / 7.1e-17   3: 1.4e-14 / 2.0e-14
     5: 3.4e-14 / 4.8e-14   8: 9.5e-15 / 1.3e-14   15: 1.9e-14 / 2.7e-14   16: 1.5e-14 / 2.2e-14   64: 5.5e-15 / 7.7e-15
+    100: 5.5e-15 / 7.8e-15   200: 3.8e-15 / 5.4e-15
     400: 8.8e-15 / 1.2e-14   1000: 1.1e-14 / 1.6e-14   1023: 9.4e-15 / 1.3e-14   1024: 1.2e-14 / 1.7e-14
     1025: 1.0e-14 / 1.4e-14   2047: 1.6e-14 / 2.3e-14   2048: 1.4e-14 / 2.0e-14   2049: 1.6e-14 / 2.3e-14
     4000: 2.4e-14 / 3.4e-14   4095: 2.3e-14 / 3.3e-14   4096: 2.6e-14 / 3.7e-14
