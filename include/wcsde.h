@@ -455,6 +455,56 @@ size_t wc_phase_conn_workspace_size(int B, int N, int64_t M, int measures);
 int wc_phase_conn(int B, int N, int64_t M, const double* phasor, const double* amp, int measures,
                   double* out, void* workspace, size_t ws_bytes, void* stream);
 
+/* Weighted graph measures of B matrices w [B][N][N] fp64, batched (wc_graph.hip; the reference's
+ * graph_utils.py, after Rubinov & Sporns): the companions of wc_hma's integration and segregation
+ * on the matrix side.  No symmetry is assumed: every expression is evaluated as the reference
+ * writes it, so a directed matrix gives what the reference gives.  One workgroup per matrix (per
+ * matrix and node for the local efficiency), everything in LDS, no workspace.
+ *
+ * Common to the three: B >= 1, 2 <= N <= 96 (more: WC_EUNSUPPORTED), w not NULL, at least one output
+ * not NULL (every output is optional on its own), no output overlapping w, every pointer 8-byte
+ * aligned (the int32 outputs too); all of it checked before any device work.
+ *
+ * wc_graph_paths: distance_wei (graph_utils.py:1462-1529) and charpath (:1533-1591) of every matrix.
+ *   w holds weights (lengths == 0: the connection lengths are L = 1/w where w != 0, as invert,
+ *   :68-90) or the lengths themselves (lengths != 0).  D starts as 0 on the diagonal, L where
+ *   L != 0 and +inf elsewhere; Floyd-Warshall gives the shortest paths.
+ *     dist  [B][N][N]  D: +inf for an unreachable pair, 0 on the diagonal
+ *     hops  [B][N][N]  int32, edges of the shortest path (the reference's B): 1 on an edge,
+ *                      h[i][k] + h[k][j] wherever D[i][k] + D[k][j] < D[i][j] strictly; 0 on the
+ *                      diagonal and for an unreachable pair
+ *     stats [B][4]     lambda = mean D, efficiency = mean 1/D, radius = min ecc, diameter = max ecc
+ *     ecc   [B][N]     row maxima of D
+ *   all over the off-diagonal entries, the infinite ones included (include_infinite != 0: one
+ *   unreachable pair makes lambda +inf and adds 0 to the efficiency, which then equals
+ *   efficiency_wei(local=False), :597-690) or dropped (include_infinite == 0; a row with nothing
+ *   left has ecc NaN and is passed over by radius and diameter, no entry at all gives lambda and
+ *   efficiency NaN).
+ *   A matrix with a negative or NaN entry (the reference is undefined there) gets NaN in every
+ *   fp64 output and -1 in hops; the other matrices of the batch are not affected.
+ *
+ * wc_graph_local_efficiency: efficiency_wei(local=True) (:667-685).  eloc [B][N]; for node u, with
+ *   V the nodes v where w[u][v] != 0 or w[v][u] != 0 and D the shortest paths within V,
+ *     e = 1/D (0 on the diagonal), se = cuberoot(e) + cuberoot(e^T),
+ *     sw = cuberoot(w[u][V]) + cuberoot(w[V][u]),  sa = (w[u][V] != 0) + (w[V][u] != 0),
+ *     E[u] = (sum_ij sw_i sw_j se_ij / 2) / ((sum sa)^2 - sum sa^2), and 0 where the numerator is 0
+ *   (no neighbour, or one).  cuberoot(x) = sign(x) |x|^(1/3) (:38-43).  Negative or NaN entries as
+ *   for wc_graph_paths: eloc of that matrix is NaN.  B N < 2^31.
+ *
+ * wc_graph_clustering: with ws = cuberoot(w), cyc3_i = sum_j (ws ws)_ij ws_ji and K_i the
+ *   non-zeros of row i,
+ *     clustering   [B][N]  cyc3_i / (K_i (K_i - 1)), exactly 0 where cyc3_i == 0 (clustering_coef_wu,
+ *                          :1305-1323)
+ *     transitivity [B]     sum cyc3 / sum K (K - 1)                     (transitivity_wu, :1673-1689)
+ *     strengths    [B][N]  column sums                                   (strengths_und, :1766-1778)
+ *     degrees      [B][N]  int32, non-zeros of a column                  (degrees_und, :1721-1737)
+ *   Negative weights are legal here: the cube root carries the sign. */
+int wc_graph_paths(int B, int N, const double* w, int lengths, int include_infinite, double* dist,
+                   int* hops, double* stats, double* ecc, void* stream);
+int wc_graph_local_efficiency(int B, int N, const double* w, double* eloc, void* stream);
+int wc_graph_clustering(int B, int N, const double* w, double* clustering, double* transitivity,
+                        double* strengths, int* degrees, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -91,6 +91,9 @@ _SIGNATURES = {
     "wc_spectrogram": (c_int, [c_i64, c_i64, c_vp, c_int, c_int, c_vp, c_int, c_dbl, c_int, c_vp, c_vp, c_sz, c_vp]),
     "wc_phase_conn_workspace_size": (c_sz, [c_int, c_int, c_i64, c_int]),
     "wc_phase_conn": (c_int, [c_int, c_int, c_i64, c_vp, c_vp, c_int, c_vp, c_vp, c_sz, c_vp]),
+    "wc_graph_paths": (c_int, [c_int, c_int, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "wc_graph_local_efficiency": (c_int, [c_int, c_int, c_vp, c_vp, c_vp]),
+    "wc_graph_clustering": (c_int, [c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
 }
 
 

@@ -1,0 +1,445 @@
+// wc_graph.hip -- weighted graph measures of a batch of N x N matrices on gfx950: shortest paths and
+// what follows from them (characteristic path length, global efficiency, eccentricity, radius,
+// diameter), local efficiency, clustering coefficient, transitivity, strengths and degrees.
+//
+// Replaces, for B matrices at once, the host loops of the reference's graph_utils.py:
+//   distance_wei (:1462-1529) + charpath (:1533-1591) + efficiency_wei(local=False) (:597-690)
+//                                                          -> wc_graph_paths
+//   efficiency_wei(local=True) (:667-685)                  -> wc_graph_local_efficiency
+//   clustering_coef_wu (:1305-1323), transitivity_wu (:1673-1689), strengths_und (:1766-1778),
+//   degrees_und (:1721-1737)                               -> wc_graph_clustering
+// No symmetry is assumed: the expressions are evaluated as the reference writes them, so a directed
+// matrix gives what the reference gives.
+//
+// Shortest paths are Floyd-Warshall in LDS, one workgroup per matrix (N <= 96), instead of the
+// reference's Dijkstra per source.  With D[k][k] = 0 and lengths >= 0, iteration k changes neither
+// row k nor column k (D[i][k] + D[k][k] is never strictly below D[i][k]), and those are all that the
+// iteration reads of other cells: the update is in place, one barrier per k.  The 256 threads form a
+// 16 x 16 grid and thread (ty, tx) keeps the cells (ty + 16 a, tx + 16 b), a, b < R = ceil(n / 16),
+// in registers: 2 R LDS reads for R^2 updates per k, an LDS write only where a path improves.
+// The hop count of the reference's B matrix rides along in LDS: 1 on an edge, h[i][k] + h[k][j]
+// where D[i][k] + D[k][j] < D[i][j] strictly (equal to Dijkstra's count where the shortest path is
+// unique).
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+#include "wc_common.h"
+
+namespace {
+
+constexpr int kMaxN = 96;
+constexpr int kThreads = 256;
+constexpr int kGrid = 16;  // threads per side of the 16 x 16 thread grid (kThreads = kGrid^2)
+
+// graph_utils.py:38-43: sign(x) |x|^(1/3).  pow, not cbrt: within an ulp or two of numpy's.
+__device__ __forceinline__ double cuberoot(double x) {
+    return x == 0.0 ? 0.0 : copysign(pow(fabs(x), 1.0 / 3.0), x);
+}
+
+// All-pairs shortest paths of D [n][n] (row stride n) in LDS, in place; H the hop counts (HOPS).
+// D is complete and the workgroup synchronised on entry and on return.  Cells past n hold 0 in
+// registers: a sum of lengths is never below it.
+template <int R, bool HOPS>
+__device__ __forceinline__ void floyd_warshall(int n, double* D, int* H) {
+    const int ty = threadIdx.x / kGrid, tx = threadIdx.x % kGrid;
+    double d[R][R];
+#pragma unroll
+    for (int a = 0; a < R; ++a)
+#pragma unroll
+        for (int b = 0; b < R; ++b) {
+            const int i = ty + kGrid * a, j = tx + kGrid * b;
+            d[a][b] = (i < n && j < n) ? D[i * n + j] : 0.0;
+        }
+    for (int k = 0; k < n; ++k) {
+        double dik[R], dkj[R];
+#pragma unroll
+        for (int a = 0; a < R; ++a) {
+            const int i = ty + kGrid * a;
+            dik[a] = i < n ? D[i * n + k] : 0.0;
+        }
+#pragma unroll
+        for (int b = 0; b < R; ++b) {
+            const int j = tx + kGrid * b;
+            dkj[b] = j < n ? D[k * n + j] : 0.0;
+        }
+#pragma unroll
+        for (int a = 0; a < R; ++a)
+#pragma unroll
+            for (int b = 0; b < R; ++b) {
+                const double s = dik[a] + dkj[b];
+                if (s < d[a][b]) {  // never for a cell past n, nor in row k or column k
+                    const int i = ty + kGrid * a, j = tx + kGrid * b;
+                    d[a][b] = s;
+                    D[i * n + j] = s;
+                    if (HOPS) H[i * n + j] = H[i * n + k] + H[k * n + j];
+                }
+            }
+        __syncthreads();
+    }
+}
+
+template <bool HOPS>
+__device__ __forceinline__ void floyd_warshall_n(int n, double* D, int* H) {
+    switch ((n + kGrid - 1) / kGrid) {
+        case 0: break;
+        case 1: floyd_warshall<1, HOPS>(n, D, H); break;
+        case 2: floyd_warshall<2, HOPS>(n, D, H); break;
+        case 3: floyd_warshall<3, HOPS>(n, D, H); break;
+        case 4: floyd_warshall<4, HOPS>(n, D, H); break;
+        case 5: floyd_warshall<5, HOPS>(n, D, H); break;
+        default: floyd_warshall<6, HOPS>(n, D, H); break;
+    }
+}
+
+// connection length of a weight (invert, graph_utils.py:68-90): 1/w where w != 0
+__device__ __forceinline__ double length_of(double w) { return w != 0.0 ? 1.0 / w : 0.0; }
+
+// ---- wc_graph_paths: one workgroup per matrix ----
+__global__ void __launch_bounds__(kThreads) paths_kernel(int N, const double* __restrict__ w_all, int lengths,
+                                                         int include_infinite, double* __restrict__ dist,
+                                                         int* __restrict__ hops, double* __restrict__ stats,
+                                                         double* __restrict__ ecc) {
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    double* D = lds;               // [N][N]
+    double* rsum = D + N * N;      // [N] row sums of D, of 1/D, row maxima, counts of entries
+    double* rinv = rsum + N;
+    double* rmax = rinv + N;
+    int* rcnt = reinterpret_cast<int*>(rmax + N);
+    int* H = rcnt + N + (N & 1);   // [N][N], only with hops
+    const int tid = threadIdx.x;
+    const size_t b = blockIdx.x;
+    const double* W = w_all + b * N * N;
+
+    int bad = 0;
+    for (int idx = tid; idx < N * N; idx += kThreads) {
+        const double x = W[idx];
+        bad |= !(x >= 0.0);  // negative or NaN
+        const int i = idx / N, j = idx % N;
+        const double L = lengths ? x : length_of(x);
+        D[idx] = i == j ? 0.0 : (L != 0.0 ? L : INFINITY);
+        if (hops) H[idx] = (i != j && L != 0.0) ? 1 : 0;
+    }
+    bad = __syncthreads_or(bad);
+    if (bad) {  // uniform: the reference is undefined here; nothing of this matrix is computed
+        for (int idx = tid; idx < N * N; idx += kThreads) {
+            if (dist) dist[b * N * N + idx] = NAN;
+            if (hops) hops[b * N * N + idx] = -1;
+        }
+        if (stats && tid < 4) stats[b * 4 + tid] = NAN;
+        if (ecc)
+            for (int i = tid; i < N; i += kThreads) ecc[b * N + i] = NAN;
+        return;
+    }
+    if (hops)
+        floyd_warshall_n<true>(N, D, H);
+    else
+        floyd_warshall_n<false>(N, D, H);
+
+    for (int idx = tid; idx < N * N; idx += kThreads) {
+        if (dist) dist[b * N * N + idx] = D[idx];
+        if (hops) hops[b * N * N + idx] = H[idx];
+    }
+    if (!stats && !ecc) return;
+    // charpath: the diagonal left out, infinite entries kept or dropped
+    if (tid < N) {
+        double s = 0.0, si = 0.0, mx = -INFINITY;
+        int c = 0;
+        for (int j = 0; j < N; ++j) {
+            const double v = D[tid * N + j];
+            if (j == tid || (!include_infinite && isinf(v))) continue;
+            s += v;
+            si += 1.0 / v;
+            mx = fmax(mx, v);
+            ++c;
+        }
+        rsum[tid] = s;
+        rinv[tid] = si;
+        rmax[tid] = c ? mx : NAN;  // a row with nothing left has no eccentricity
+        rcnt[tid] = c;
+        if (ecc) ecc[b * N + tid] = rmax[tid];
+    }
+    __syncthreads();
+    if (stats && tid == 0) {
+        double s = 0.0, si = 0.0, lo = NAN, hi = NAN;  // fmin / fmax pass over the rows without one
+        int c = 0;
+        for (int i = 0; i < N; ++i) {
+            s += rsum[i];
+            si += rinv[i];
+            c += rcnt[i];
+            lo = fmin(lo, rmax[i]);
+            hi = fmax(hi, rmax[i]);
+        }
+        stats[b * 4 + 0] = s / c;  // no entry at all: 0/0 = NaN, numpy's mean of nothing
+        stats[b * 4 + 1] = si / c;
+        stats[b * 4 + 2] = lo;
+        stats[b * 4 + 3] = hi;
+    }
+}
+
+size_t paths_lds_bytes(int N, bool hops) {
+    return sizeof(double) * ((size_t)N * N + 3 * N) + sizeof(int) * (N + (N & 1) + (hops ? (size_t)N * N : 0));
+}
+
+// ---- wc_graph_local_efficiency: one workgroup per (matrix, node u) ----
+__global__ void __launch_bounds__(kThreads) local_efficiency_kernel(int N, const double* __restrict__ w_all,
+                                                                    double* __restrict__ eloc) {
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    double* D = lds;                                   // [k][k] lengths, distances, then cuberoot(1/D)
+    double* sw = D + N * N;                            // [N] symmetrised cube-root weights to u
+    double* red = sw + N;                              // [kThreads]
+    int* nb = reinterpret_cast<int*>(red + kThreads);  // [N] is v a neighbour of u
+    int* V = nb + N;                                   // [N] the neighbours, ascending
+    int* sa = V + N;                                   // [N] symmetrised adjacency to u
+    const int tid = threadIdx.x;
+    const size_t b = blockIdx.x / N;
+    const int u = blockIdx.x % N;
+    const double* W = w_all + b * N * N;
+
+    int bad = 0;
+    for (int idx = tid; idx < N * N; idx += kThreads) bad |= !(W[idx] >= 0.0);
+    if (tid < N) nb[tid] = (W[u * N + tid] != 0.0 || W[tid * N + u] != 0.0) ? 1 : 0;
+    bad = __syncthreads_or(bad);
+    if (bad) {
+        if (tid == 0) eloc[b * N + u] = NAN;
+        return;
+    }
+    int k = 0;
+    for (int v = 0; v < N; ++v) k += nb[v];
+    if (tid < N && nb[tid]) {
+        int pos = 0;
+        for (int v = 0; v < tid; ++v) pos += nb[v];
+        V[pos] = tid;
+        const double out = W[u * N + tid], in = W[tid * N + u];
+        sw[pos] = cuberoot(out) + cuberoot(in);
+        sa[pos] = (out != 0.0) + (in != 0.0);
+    }
+    __syncthreads();
+    // lengths among the neighbours: paths stay inside the neighbourhood
+    for (int idx = tid; idx < k * k; idx += kThreads) {
+        const int a = idx / k, c = idx % k;
+        const double L = length_of(W[V[a] * N + V[c]]);
+        D[idx] = a == c ? 0.0 : (L != 0.0 ? L : INFINITY);
+    }
+    __syncthreads();
+    floyd_warshall_n<false>(k, D, nullptr);
+    // e = 1/D with a zero diagonal (1/inf = 0), se = cuberoot(e) + cuberoot(e^T)
+    for (int idx = tid; idx < k * k; idx += kThreads) D[idx] = idx / k == idx % k ? 0.0 : cuberoot(1.0 / D[idx]);
+    __syncthreads();
+    double part = 0.0;
+    for (int idx = tid; idx < k * k; idx += kThreads) {
+        const int a = idx / k, c = idx % k;
+        part += sw[a] * sw[c] * (D[a * k + c] + D[c * k + a]);
+    }
+    red[tid] = part;
+    __syncthreads();
+    for (int o = kThreads / 2; o > 0; o >>= 1) {
+        if (tid < o) red[tid] += red[tid + o];
+        __syncthreads();
+    }
+    if (tid == 0) {
+        const double numer = red[0] / 2;
+        long long s1 = 0, s2 = 0;
+        for (int a = 0; a < k; ++a) {
+            s1 += sa[a];
+            s2 += sa[a] * sa[a];
+        }
+        // no neighbour or one: numer is exactly 0 and so is E
+        eloc[b * N + u] = numer != 0.0 ? numer / (double)(s1 * s1 - s2) : 0.0;
+    }
+}
+
+size_t local_efficiency_lds_bytes(int N) {
+    return sizeof(double) * ((size_t)N * N + N + kThreads) + sizeof(int) * 3 * (size_t)N;
+}
+
+// ---- wc_graph_clustering: one workgroup per matrix ----
+// cyc3_i = sum_j (ws ws)_ij ws_ji with ws = cuberoot(w) in LDS, padded by zeros to Np, whole 16-tiles.
+// Thread (ty, tx) of the 16 x 16 grid accumulates the R x R cells (ty + 16 a, tx + 16 b) of ws ws in
+// registers, multiplies by ws^T and sums its rows; the 16 lanes of one ty then add up by shuffles.
+// (The same product on v_mfma_f64_16x16x4_f64, 16 x 16 tiles dealt to the four waves, measured
+// slower: 4.73 ms against 3.90 ms for 20,000 matrices of 90 nodes, docs/CHANGELOG.md.  The MI355X data
+// sheet gives vector and matrix fp64 the same peak, and the tiles' A and B operands come from LDS
+// one double per lane per MFMA, without the register reuse of the R x R cells.)
+template <int R>
+__device__ __forceinline__ void cyc3_rows(int Np, const double* S, double* cyc3) {
+    const int ty = threadIdx.x / kGrid, tx = threadIdx.x % kGrid;
+    double acc[R][R];
+#pragma unroll
+    for (int a = 0; a < R; ++a)
+#pragma unroll
+        for (int c = 0; c < R; ++c) acc[a][c] = 0.0;
+    for (int k = 0; k < Np; ++k) {
+        double sik[R], skj[R];
+#pragma unroll
+        for (int a = 0; a < R; ++a) sik[a] = S[(ty + kGrid * a) * Np + k];
+#pragma unroll
+        for (int c = 0; c < R; ++c) skj[c] = S[k * Np + tx + kGrid * c];
+#pragma unroll
+        for (int a = 0; a < R; ++a)
+#pragma unroll
+            for (int c = 0; c < R; ++c) acc[a][c] = fma(sik[a], skj[c], acc[a][c]);
+    }
+#pragma unroll
+    for (int a = 0; a < R; ++a) {
+        const int i = ty + kGrid * a;
+        double v = 0.0;
+#pragma unroll
+        for (int c = 0; c < R; ++c) v = fma(acc[a][c], S[(tx + kGrid * c) * Np + i], v);
+        for (int o = kGrid / 2; o > 0; o >>= 1) v += __shfl_xor(v, o);
+        if (tx == 0) cyc3[i] = v;
+    }
+}
+
+__device__ __forceinline__ void cyc3_all(int Np, const double* S, double* cyc3) {
+    switch (Np / kGrid) {
+        case 1: cyc3_rows<1>(Np, S, cyc3); break;
+        case 2: cyc3_rows<2>(Np, S, cyc3); break;
+        case 3: cyc3_rows<3>(Np, S, cyc3); break;
+        case 4: cyc3_rows<4>(Np, S, cyc3); break;
+        case 5: cyc3_rows<5>(Np, S, cyc3); break;
+        default: cyc3_rows<6>(Np, S, cyc3); break;
+    }
+    __syncthreads();
+}
+
+__global__ void __launch_bounds__(kThreads) clustering_kernel(int N, const double* __restrict__ w_all,
+                                                              double* __restrict__ clustering,
+                                                              double* __restrict__ transitivity,
+                                                              double* __restrict__ strengths,
+                                                              int* __restrict__ degrees) {
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    const int Np = (N + 15) / 16 * 16;
+    double* S = lds;               // [Np][Np] cuberoot(w), zero padded
+    double* cyc3 = S + Np * Np;    // [Np]
+    int* K = reinterpret_cast<int*>(cyc3 + Np);  // [N] non-zeros of a row
+    const int tid = threadIdx.x;
+    const size_t b = blockIdx.x;
+    const double* W = w_all + b * N * N;
+
+    // strengths_und and degrees_und: column sums and column counts of non-zeros; K: row counts
+    if (tid < N) {
+        double s = 0.0;
+        int deg = 0, k = 0;
+        for (int r = 0; r < N; ++r) {
+            const double x = W[r * N + tid];  // coalesced over tid
+            s += x;
+            deg += x != 0.0;
+        }
+        if (strengths) strengths[b * N + tid] = s;
+        if (degrees) degrees[b * N + tid] = deg;
+        if (clustering || transitivity) {
+            for (int c = 0; c < N; ++c) k += !(W[tid * N + c] == 0.0);  // logical_not(W == 0): NaN counts
+            K[tid] = k;
+        }
+    }
+    if (!clustering && !transitivity) return;
+    for (int idx = tid; idx < Np * Np; idx += kThreads) {
+        const int i = idx / Np, j = idx % Np;
+        S[idx] = (i < N && j < N) ? cuberoot(W[i * N + j]) : 0.0;
+    }
+    __syncthreads();
+    cyc3_all(Np, S, cyc3);
+    if (clustering && tid < N) {
+        const double k = (double)K[tid];
+        clustering[b * N + tid] = cyc3[tid] == 0.0 ? 0.0 : cyc3[tid] / (k * (k - 1.0));
+    }
+    if (transitivity && tid == 0) {
+        double s = 0.0;
+        long long kk = 0;
+        for (int i = 0; i < N; ++i) {
+            s += cyc3[i];
+            kk += (long long)K[i] * (K[i] - 1);
+        }
+        transitivity[b] = s / (double)kk;
+    }
+}
+
+size_t clustering_lds_bytes(int N) {
+    const size_t Np = (size_t)(N + 15) / 16 * 16;
+    return sizeof(double) * (Np * Np + Np) + sizeof(int) * (size_t)N;
+}
+
+// ---- argument checks shared by the three entry points ----
+struct Out {
+    const void* p;
+    size_t bytes;  // of the whole output
+};
+
+int check_args(const char* name, int B, int N, const double* w, const Out* outs, int nouts, bool per_node_grid) {
+    char msg[200];
+    if (B < 1) return snprintf(msg, sizeof msg, "%s: B < 1", name), wc_set_err(WC_EINVAL, msg);
+    if (N < 2) return snprintf(msg, sizeof msg, "%s: N < 2", name), wc_set_err(WC_EINVAL, msg);
+    if (N > kMaxN) {
+        snprintf(msg, sizeof msg, "%s: N = %d > 96 (one matrix per workgroup, in LDS)", name, N);
+        return wc_set_err(WC_EUNSUPPORTED, msg);
+    }
+    if (!w) return snprintf(msg, sizeof msg, "%s: w is NULL", name), wc_set_err(WC_EINVAL, msg);
+    if (per_node_grid && (int64_t)B * N > INT32_MAX)
+        return snprintf(msg, sizeof msg, "%s: 2^31 workgroups or more (B times N)", name), wc_set_err(WC_EINVAL, msg);
+    bool any = false;
+    for (int k = 0; k < nouts; ++k) any = any || outs[k].p;
+    if (!any) return snprintf(msg, sizeof msg, "%s: every output is NULL", name), wc_set_err(WC_EINVAL, msg);
+    const uintptr_t w0 = (uintptr_t)w, w1 = w0 + (size_t)B * N * N * sizeof(double);
+    if (w0 & 7) return snprintf(msg, sizeof msg, "%s: w must be 8-byte aligned", name), wc_set_err(WC_EINVAL, msg);
+    for (int k = 0; k < nouts; ++k) {
+        if (!outs[k].p) continue;
+        const uintptr_t p0 = (uintptr_t)outs[k].p, p1 = p0 + outs[k].bytes;
+        if (p0 < w1 && w0 < p1)
+            return snprintf(msg, sizeof msg, "%s: an output must not alias w", name), wc_set_err(WC_EINVAL, msg);
+        if (p0 & 7)
+            return snprintf(msg, sizeof msg, "%s: every output must be 8-byte aligned", name), wc_set_err(WC_EINVAL, msg);
+    }
+    return WC_OK;
+}
+
+template <typename Kernel>
+int raise_lds(Kernel kernel, size_t lds) {
+    if (lds <= 65536) return WC_OK;
+    hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    return e == hipSuccess ? WC_OK : wc_set_err(WC_EHIP, hipGetErrorString(e));
+}
+
+}  // namespace
+
+extern "C" {
+
+int wc_graph_paths(int B, int N, const double* w, int lengths, int include_infinite, double* dist, int* hops,
+                   double* stats, double* ecc, void* stream) {
+    wc_clear_err();
+    const size_t b = B > 0 ? (size_t)B : 0, n = N > 0 ? (size_t)N : 0;
+    const Out outs[4] = {{dist, b * n * n * 8}, {hops, b * n * n * 4}, {stats, b * 4 * 8}, {ecc, b * n * 8}};
+    if (int rc = check_args("wc_graph_paths", B, N, w, outs, 4, false)) return rc;
+    const size_t lds = paths_lds_bytes(N, hops != nullptr);
+    if (int rc = raise_lds(paths_kernel, lds)) return rc;
+    hipLaunchKernelGGL(paths_kernel, dim3(B), dim3(kThreads), lds, static_cast<hipStream_t>(stream), N, w, lengths,
+                       include_infinite, dist, hops, stats, ecc);
+    return wc_hip_check("wc_graph_paths");
+}
+
+int wc_graph_local_efficiency(int B, int N, const double* w, double* eloc, void* stream) {
+    wc_clear_err();
+    const size_t b = B > 0 ? (size_t)B : 0, n = N > 0 ? (size_t)N : 0;
+    const Out outs[1] = {{eloc, b * n * 8}};
+    if (int rc = check_args("wc_graph_local_efficiency", B, N, w, outs, 1, true)) return rc;
+    const size_t lds = local_efficiency_lds_bytes(N);
+    if (int rc = raise_lds(local_efficiency_kernel, lds)) return rc;
+    hipLaunchKernelGGL(local_efficiency_kernel, dim3((unsigned)(B * N)), dim3(kThreads), lds,
+                       static_cast<hipStream_t>(stream), N, w, eloc);
+    return wc_hip_check("wc_graph_local_efficiency");
+}
+
+int wc_graph_clustering(int B, int N, const double* w, double* clustering, double* transitivity, double* strengths,
+                        int* degrees, void* stream) {
+    wc_clear_err();
+    const size_t b = B > 0 ? (size_t)B : 0, n = N > 0 ? (size_t)N : 0;
+    const Out outs[4] = {{clustering, b * n * 8}, {transitivity, b * 8}, {strengths, b * n * 8},
+                         {degrees, b * n * 4}};
+    if (int rc = check_args("wc_graph_clustering", B, N, w, outs, 4, false)) return rc;
+    const size_t lds = clustering_lds_bytes(N);
+    if (int rc = raise_lds(clustering_kernel, lds)) return rc;
+    hipLaunchKernelGGL(clustering_kernel, dim3(B), dim3(kThreads), lds, static_cast<hipStream_t>(stream), N, w,
+                       clustering, transitivity, strengths, degrees);
+    return wc_hip_check("wc_graph_clustering");
+}
+
+}  // extern "C"

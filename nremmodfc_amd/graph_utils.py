@@ -1,9 +1,14 @@
-"""The three graph_utils helpers the SC optimiser uses (graph_utils.py:92-164).
+"""The three graph_utils helpers the SC optimiser uses (graph_utils.py:92-164), and
+the weighted, undirected core of the reference's graph measures on the device.
 
-Same call surface and results as the reference's get_uptri, matrix_recon and
-thresholding (the rest of its 2,600-line toolbox is analysis outside the sweep
-path).  Host numpy on N x N matrices: O(N^2) bookkeeping
-once per optimiser iteration.
+get_uptri, matrix_recon and thresholding: same call surface and results as the
+reference's, host numpy on N x N matrices, O(N^2) bookkeeping once per optimiser
+iteration.  distance_wei, efficiency_wei, clustering_coef_wu, transitivity_wu,
+strengths_und and degrees_und (with cuberoot, invert and the host charpath) run
+on the device through sigchain.graph_measures, for one matrix or a [B, N, N]
+stack; torch and the library are imported on first use, so importing this module
+stays light.  The rest of the 2,600-line toolbox (modularity, betweenness, rich
+club, signed and directed variants) is analysis outside the sweep path.
 """
 import numpy as np
 
@@ -47,3 +52,105 @@ def thresholding(x, threshold=0.20, zero_diag=True, direct="undirected"):
         out[keep] = xv[keep]
         return matrix_recon(out)
     raise ValueError("Invalid type of matrix -> direct options: undirected or directed")
+
+
+# ---- weighted graph measures on the device (sigchain.graph_measures) ----
+# The reference's call surface and return shapes for one N x N matrix; as an extension a [B, N, N]
+# stack gives stacked results from one batched launch.  torch and the library load on first use.
+
+GRAPH_MAX_N = 96  # sigchain.GRAPH_MAX_N: one matrix per workgroup, in LDS
+
+
+def cuberoot(x):
+    """sign(x) |x|^(1/3) (graph_utils.py:38-43)."""
+    x = np.asarray(x, dtype=np.float64)
+    r = np.abs(x) ** (1 / 3)
+    return np.where(x < 0, -r, r)
+
+
+def invert(W, copy=True):
+    """1/W where W != 0: weights to lengths (graph_utils.py:68-90); in place with copy=False."""
+    out = W.copy() if copy else W
+    nz = out != 0
+    out[nz] = 1.0 / out[nz]
+    return out
+
+
+def _matrices(name, W, nonnegative):
+    """W as a contiguous fp64 [N][N] or [B][N][N] array, refused here where the device would refuse it."""
+    a = np.ascontiguousarray(W, dtype=np.float64)
+    if a.ndim not in (2, 3) or a.shape[-1] != a.shape[-2] or a.shape[0] == 0:
+        raise ValueError(f"{name}: needs an N x N matrix or a [B, N, N] stack, got shape {a.shape}")
+    N = a.shape[-1]
+    if N < 2 or N > GRAPH_MAX_N:
+        raise ValueError(f"{name}: N = {N}, the device kernels take 2 <= N <= {GRAPH_MAX_N}")
+    if nonnegative and not (a >= 0).all():
+        raise ValueError(f"{name}: negative or NaN entries (the shortest paths are undefined)")
+    return a
+
+
+def _device(a, names, **kw):
+    import torch
+
+    from . import sigchain
+    got = sigchain.graph_measures(torch.from_numpy(a).cuda(), names, **kw)
+    return [got[m].cpu().numpy() for m in names]
+
+
+def distance_wei(G):
+    """(D, B): shortest weighted paths over the connection lengths G and their numbers of edges
+    (graph_utils.py:1462-1529); inf and 0 for an unreachable pair."""
+    D, B = _device(_matrices("distance_wei", G, True), ("dist", "hops"), lengths=True)
+    return D, B.astype(np.float64)
+
+
+def charpath(D, include_diagonal=False, include_infinite=True):
+    """(lambda, efficiency, ecc, radius, diameter) of a distance matrix (graph_utils.py:1533-1591), on
+    the host: O(N^2).  A row of which the two flags leave nothing has ecc NaN and is passed over by
+    radius and diameter (the reference's masked maximum leaves numpy's fill value there)."""
+    D = np.asarray(D, dtype=np.float64)
+    if D.ndim == 3:
+        lam, eff, ecc, rad, dia = zip(*(charpath(d, include_diagonal, include_infinite) for d in D))
+        return np.array(lam), np.array(eff), np.array(ecc), np.array(rad), np.array(dia)
+    keep = ~np.isnan(D)
+    if not include_diagonal:
+        keep &= ~np.eye(D.shape[0], dtype=bool)
+    if not include_infinite:
+        keep &= ~np.isinf(D)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        v = D[keep]
+        lam = v.mean() if v.size else np.nan
+        eff = (1 / v).mean() if v.size else np.nan
+    ecc = np.array([row[k].max() if k.any() else np.nan for row, k in zip(D, keep)])
+    some = ecc[~np.isnan(ecc)]
+    return lam, eff, ecc, (some.min() if some.size else np.nan), (some.max() if some.size else np.nan)
+
+
+def efficiency_wei(Gw, local=False):
+    """Global efficiency (a float) or, with local=True, the local efficiency of every node
+    (graph_utils.py:597-690)."""
+    a = _matrices("efficiency_wei", Gw, True)
+    E, = _device(a, ("local_efficiency" if local else "efficiency",))
+    return E if local or a.ndim == 3 else float(E)
+
+
+def clustering_coef_wu(W):
+    """Weighted clustering coefficient of every node (graph_utils.py:1305-1323)."""
+    return _device(_matrices("clustering_coef_wu", W, False), ("clustering",))[0]
+
+
+def transitivity_wu(W):
+    """Weighted transitivity (graph_utils.py:1673-1689)."""
+    a = _matrices("transitivity_wu", W, False)
+    T, = _device(a, ("transitivity",))
+    return T if a.ndim == 3 else float(T)
+
+
+def strengths_und(CIJ):
+    """Node strengths: column sums (graph_utils.py:1766-1778)."""
+    return _device(_matrices("strengths_und", CIJ, False), ("strengths",))[0]
+
+
+def degrees_und(CIJ):
+    """Node degrees: non-zeros of every column (graph_utils.py:1721-1737)."""
+    return _device(_matrices("degrees_und", CIJ, False), ("degrees",))[0].astype(np.float64)

@@ -1,8 +1,8 @@
 """Device-side signal chain: BOLD + band-pass filtfilt + decimation, FC and
 goodness of fit, Kuramoto, Welch peak, band-limited amplitude envelopes, Welch
 spectra per column, cross spectra and coherence between columns, spectrograms
-per column, phase and envelope connectivity between columns -- thin wrappers
-over libwcsde.so.
+per column, phase and envelope connectivity between columns, HMA and the
+weighted graph measures of the FC matrices -- thin wrappers over libwcsde.so.
 
 References: simBOLD netwWilsonCowanPlastic.py:140-158; np.corrcoef
 whole_sweep_both.py:81; utils.get_all_metrics / kuramoto utils.py:34-50; Welch
@@ -318,6 +318,78 @@ class WelchAccumulator:
         _lib.check(_lib.lib().wc_welch_peak(self.B, self.N, self.nseg, fs, _lib.ptr(self.acc), _lib.ptr(peak),
                                             _lib.ptr(psd), _lib.stream_handle()), "wc_welch_peak")
         return peak, psd
+
+
+GRAPH_MAX_N = 96    # wc_graph_*: one matrix per workgroup, in LDS
+GRAPH_PATH_MEASURES = ("dist", "hops", "charpath", "efficiency", "ecc", "radius", "diameter")  # wc_graph_paths
+GRAPH_CLUSTER_MEASURES = ("clustering", "transitivity", "strengths", "degrees")                # wc_graph_clustering
+GRAPH_MEASURES = GRAPH_PATH_MEASURES + ("local_efficiency",) + GRAPH_CLUSTER_MEASURES
+_GRAPH_STATS = {"charpath": 0, "efficiency": 1, "radius": 2, "diameter": 3}  # columns of wc_graph_paths' stats
+
+
+def graph_measures(w, measures=GRAPH_MEASURES, lengths=False, include_infinite=True):
+    """Weighted graph measures of B matrices on the device (the reference's graph_utils.py, after
+    Rubinov & Sporns): w [B][N][N] or [N][N] fp64 device tensor, 2 <= N <= 96 -> a dict from measure
+    name to a device tensor ([B] leading, or without it for a single matrix).  No symmetry is assumed.
+
+    From wc_graph_paths (distance_wei + charpath): "dist" [N][N] shortest weighted paths over the
+    lengths 1/w (w itself with lengths=True), +inf where there is none; "hops" [N][N] int32, their
+    edges; "charpath" and "efficiency", the means of D and 1/D off the diagonal (the latter is
+    efficiency_wei(local=False)); "ecc" [N], "radius", "diameter".  include_infinite=False leaves the
+    infinite distances out of those means and maxima.  "local_efficiency" [N] from
+    wc_graph_local_efficiency (efficiency_wei(local=True)).  From wc_graph_clustering: "clustering" [N]
+    (clustering_coef_wu), "transitivity" (transitivity_wu), "strengths" [N] (strengths_und), "degrees"
+    [N] int32 (degrees_und).  Only the kernels that the asked measures need are launched.  A matrix with
+    a negative or NaN entry has NaN (hops: -1) in the path measures and the local efficiency.
+    lengths=True goes with the path measures only: the others are defined on weights.
+
+    Composes with fc_metrics(..., want_fc=True) and hma: both leave FC matrices of this layout."""
+    names = (measures,) if isinstance(measures, str) else tuple(measures)
+    for m in names:
+        if m not in GRAPH_MEASURES:
+            raise ValueError(f"graph_measures: unknown measure {m!r}, must be one of {list(GRAPH_MEASURES)}")
+    if not names:
+        raise ValueError(f"graph_measures: no measure asked for, choose from {list(GRAPH_MEASURES)}")
+    names = tuple(dict.fromkeys(names))
+    if lengths and any(m not in GRAPH_PATH_MEASURES for m in names):
+        raise ValueError(f"graph_measures: lengths=True goes with the path measures {list(GRAPH_PATH_MEASURES)} "
+                         "only, the others are defined on weights")
+    if not isinstance(w, torch.Tensor) or w.dtype != torch.float64 or w.dim() not in (2, 3) \
+            or w.shape[-1] != w.shape[-2]:
+        raise TypeError("graph_measures: w must be a [B][N][N] or [N][N] fp64 device tensor")
+    single = w.dim() == 2
+    B, N = (1 if single else w.shape[0]), w.shape[-1]
+    if N < 2 or N > GRAPH_MAX_N or B < 1:
+        raise ValueError(f"graph_measures: N = {N}, B = {B}: needs B >= 1 and 2 <= N <= {GRAPH_MAX_N} "
+                         "(one matrix per workgroup, in LDS)")
+    L = _lib.lib()
+    w = w.contiguous()
+    dev, st = w.device, _lib.stream_handle()
+    want = set(names)
+
+    def new(key, *shape, dtype=torch.float64):
+        return torch.empty((B,) + shape, dtype=dtype, device=dev) if want & set(key) else None
+
+    res = {}
+    if want & set(GRAPH_PATH_MEASURES):
+        dist, hops = new(("dist",), N, N), new(("hops",), N, N, dtype=torch.int32)
+        stats, ecc = new(tuple(_GRAPH_STATS), 4), new(("ecc",), N)
+        _lib.check(L.wc_graph_paths(B, N, _lib.ptr(w), int(bool(lengths)), int(bool(include_infinite)), _lib.ptr(dist),
+                                    _lib.ptr(hops), _lib.ptr(stats), _lib.ptr(ecc), st), "wc_graph_paths")
+        res.update(dist=dist, hops=hops, ecc=ecc)
+        if stats is not None:
+            res.update({m: stats[:, k] for m, k in _GRAPH_STATS.items()})
+    if "local_efficiency" in want:
+        res["local_efficiency"] = new(("local_efficiency",), N)
+        _lib.check(L.wc_graph_local_efficiency(B, N, _lib.ptr(w), _lib.ptr(res["local_efficiency"]), st),
+                   "wc_graph_local_efficiency")
+    if want & set(GRAPH_CLUSTER_MEASURES):
+        clus, trans = new(("clustering",), N), new(("transitivity",))
+        stre, deg = new(("strengths",), N), new(("degrees",), N, dtype=torch.int32)
+        _lib.check(L.wc_graph_clustering(B, N, _lib.ptr(w), _lib.ptr(clus), _lib.ptr(trans), _lib.ptr(stre),
+                                         _lib.ptr(deg), st), "wc_graph_clustering")
+        res.update(clustering=clus, transitivity=trans, strengths=stre, degrees=deg)
+    return {m: (res[m][0] if single else res[m]) for m in names}
 
 
 def welch_peak(E_t, fs=500.0, want_psd=False):
