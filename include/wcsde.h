@@ -505,6 +505,45 @@ int wc_graph_local_efficiency(int B, int N, const double* w, double* eloc, void*
 int wc_graph_clustering(int B, int N, const double* w, double* clustering, double* transitivity,
                         double* strengths, int* degrees, void* stream);
 
+/* Dynamic functional connectivity (wc_fcd.hip): sliding-window FC with its FCD matrix (Hansen et al.
+ * 2015) and the phase-coherence FCD (Deco & Kringelbach 2016).  The reference computes neither; these
+ * definitions are the contract (tests/fcd_reference.py restates them in numpy).
+ *
+ * wc_fcd: x [M][B][N] fp64, time-major (wc_fc_metrics' layout), window length win, step step.
+ *   nw = (M - win) / step + 1 windows; window k is rows k step .. k step + win - 1; trailing rows that
+ *   fit no window are not read.  FC_k = np.corrcoef(x[k step : k step + win, b, :].T) (each window
+ *   centred on its own column means before the products, clipped to [-1, 1]); its pattern v_k is the
+ *   strict upper triangle, row-major (utils.flat_FC's order), P = N (N - 1) / 2 entries.
+ *     fcd   [B][nw][nw]  fcd[b][k][l] = Pearson correlation of v_k and v_l (two passes, clipped to
+ *                        [-1, 1]): one triangle computed and mirrored, so exactly symmetric; the
+ *                        diagonal exactly 1 where defined
+ *     winfc [B][nw][P]   the patterns v_k, or NULL
+ *   A column that is constant within a window (its centred values all exactly 0) makes the entries
+ *   of v_k that involve it NaN (0 / 0, as numpy); row and column k of fcd, the diagonal included, are
+ *   then NaN, as for a pattern without variance.  No other window and no other simulation changes.
+ *   3 <= N <= 96 (more: WC_EUNSUPPORTED), 2 <= win <= M, step >= 1, nw <= WC_FCD_MAX_WINDOWS (more:
+ *   WC_EUNSUPPORTED); x, fcd and the workspace not NULL, every pointer 8-byte aligned, nothing
+ *   overlapping; all of it checked before any device work.
+ *   Workspace: wc_fcd_workspace_size() bytes (0: bad shape) hold the centred patterns and norms of
+ *   min(B, 8) simulations, (nw P + nw) doubles each; the batch goes through it in chunks, a larger
+ *   workspace takes more simulations a chunk.  Less: WC_EWORKSPACE.
+ *   Every output of simulation b depends on that simulation's data, M, win and step only, bit for
+ *   bit: not on B, on b, or on ws_bytes.  Every sum has one fixed order; no atomics.
+ *
+ * wc_fcd_phase: phasor [M][B][N][2] fp64, wc_hilbert_phase's unit phasors (c, s).  With
+ *   d_t[i][j] = cos(theta_i(t) - theta_j(t)) = c_i c_j + s_i s_j,
+ *     fcd [B][M][M]  the cosine similarity of the strict upper triangles of d_t and d_u, clipped to
+ *                    [-1, 1]; exactly symmetric, the diagonal exactly 1, NaN in row and column t
+ *                    (diagonal included) where the norm of d_t is 0 or not finite
+ *   2 <= N <= 96 (more: WC_EUNSUPPORTED), 1 <= M <= WC_FCD_PHASE_MAX_M (more: WC_EUNSUPPORTED);
+ *   pointers not NULL, 8-byte aligned, not overlapping.  No workspace; bits as for wc_fcd. */
+#define WC_FCD_MAX_WINDOWS 4096  /* wc_fcd: windows (fcd is nw x nw a simulation) */
+#define WC_FCD_PHASE_MAX_M 4096  /* wc_fcd_phase: samples (fcd is M x M a simulation) */
+size_t wc_fcd_workspace_size(int B, int N, int M, int win, int step);
+int wc_fcd(int B, int N, int M, const double* x, int win, int step, double* fcd, double* winfc,
+           void* workspace, size_t ws_bytes, void* stream);
+int wc_fcd_phase(int B, int N, int M, const double* phasor, double* fcd, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -32,7 +32,7 @@ import numpy as np
 import torch
 
 from .model import F32, Batch, Schedule, WCParams, driver_params
-from .sigchain import NEQ, WELCH_HOP, WELCH_NPERSEG, BoldStream, WelchAccumulator, fc_metrics
+from .sigchain import NEQ, WELCH_HOP, WELCH_NPERSEG, BoldStream, WelchAccumulator, fc_metrics, fcd
 
 STATES = ("W", "N1", "N2", "N3")
 
@@ -49,6 +49,7 @@ class SweepResult:
     fc: Optional[np.ndarray] = None     # [B][N][N] when requested
     bold: Optional[np.ndarray] = None   # [M][B][N] when requested
     timings: Optional[dict] = None
+    fcd: Optional[np.ndarray] = None    # [B][nw][nw] when requested (want_fcd)
 
     def columns(self):
         """The 16 metric columns of the reference's TSV rows (whole_sweep_both.py:115-116)."""
@@ -78,8 +79,12 @@ def check_supported(N, schedule: Schedule = None, chunk_samples: int = 2000):
 def run_sweep(sc, G, sigmaE, keys, empfcs: Dict[str, np.ndarray] = None, schedule: Schedule = None,
               params: WCParams = None, precision: str = F32, chunk_samples: int = 2000,
               bold_downsamp: int = 1000, max_launch_steps: int = 500_000, want_fc=False, want_bold=False,
-              device="cuda", progress=None, init_state: Optional[Dict[str, np.ndarray]] = None) -> SweepResult:
+              device="cuda", progress=None, init_state: Optional[Dict[str, np.ndarray]] = None,
+              want_fcd=None) -> SweepResult:
     """Run B simulations end to end and return the reference's per-simulation outputs.
+
+    want_fcd: None, or (window, step) in BOLD samples: SweepResult.fcd [B][nw][nw], the FCD matrix of
+    every simulation's BOLD (sigchain.fcd), computed in the epilogue beside the FC metrics.
 
     init_state: optional {"E", "I", "A"} -> [B][N] initial state instead of run()'s
     (0.1, 0.1, a_ie_0) (wc:90-99), e.g. to measure how a perturbation propagates."""
@@ -87,6 +92,8 @@ def run_sweep(sc, G, sigmaE, keys, empfcs: Dict[str, np.ndarray] = None, schedul
     p = params or driver_params()
     R = sch.rec_every
     check_supported(np.asarray(sc).shape[0], sch, chunk_samples)
+    if want_fcd is not None and len(want_fcd) != 2:
+        raise ValueError("want_fcd must be None or (window, step)")
     T = sch.n_sim // R  # recorded samples = len(wc.time)
     t_start = time.perf_counter()
     bt = Batch(sc, G, sigmaE, keys, p, precision, device)
@@ -141,6 +148,7 @@ def run_sweep(sc, G, sigmaE, keys, empfcs: Dict[str, np.ndarray] = None, schedul
     emp = np.stack([empfcs[s] for s in states]) if states else None
     bold_out = bold.finish()  # [M][C]
     fc, met, extra = fc_metrics(bold_out, B, N, emp, kuramoto=True, want_fc=want_fc)
+    fcd_out = fcd(bold_out.view(-1, B, N), want_fcd[0], want_fcd[1]) if want_fcd is not None else None
     peak = welch.peak()[0] if welch is not None else torch.full((B,), float("nan"), device=bt.device)
     torch.cuda.synchronize(bt.device)
     t_end = time.perf_counter()
@@ -150,4 +158,5 @@ def run_sweep(sc, G, sigmaE, keys, empfcs: Dict[str, np.ndarray] = None, schedul
                        fc=fc.cpu().numpy() if want_fc else None,
                        bold=bold_out.reshape(-1, B, N).cpu().numpy() if want_bold else None,
                        timings={"integrate_and_stream_s": t_sde - t_start, "epilogue_s": t_end - t_sde,
-                                "node_steps": B * N * sch.n_total})
+                                "node_steps": B * N * sch.n_total},
+                       fcd=fcd_out.cpu().numpy() if want_fcd is not None else None)

@@ -1,8 +1,9 @@
 """Device-side signal chain: BOLD + band-pass filtfilt + decimation, FC and
 goodness of fit, Kuramoto, Welch peak, band-limited amplitude envelopes, Welch
 spectra per column, cross spectra and coherence between columns, spectrograms
-per column, phase and envelope connectivity between columns, HMA and the
-weighted graph measures of the FC matrices -- thin wrappers over libwcsde.so.
+per column, phase and envelope connectivity between columns, sliding-window FC
+and FCD, HMA and the weighted graph measures of the FC matrices -- thin wrappers
+over libwcsde.so.
 
 References: simBOLD netwWilsonCowanPlastic.py:140-158; np.corrcoef
 whole_sweep_both.py:81; utils.get_all_metrics / kuramoto utils.py:34-50; Welch
@@ -390,6 +391,136 @@ def graph_measures(w, measures=GRAPH_MEASURES, lengths=False, include_infinite=T
                                          _lib.ptr(deg), st), "wc_graph_clustering")
         res.update(clustering=clus, transitivity=trans, strengths=stre, degrees=deg)
     return {m: (res[m][0] if single else res[m]) for m in names}
+
+
+FCD_MAX_N = 96            # wc_fcd, wc_fcd_phase: one window's correlation matrix, a tile's phasors per workgroup
+FCD_MAX_WINDOWS = 4096    # WC_FCD_MAX_WINDOWS
+FCD_PHASE_MAX_M = 4096    # WC_FCD_PHASE_MAX_M
+FCD_WS_CAP = 1 << 30      # wc_fcd: workspace ceiling (chunks of simulations beyond it)
+FCD_METHODS = ("corr", "phase")
+
+
+def fcd(x, window=None, step=None, method="corr", want_windows=False, trim=0, ws_bytes=None):
+    """Functional connectivity dynamics of B simulations on the device: x [M][C] (one simulation)
+    or [M][B][N] fp64 device tensor, time-major.
+
+    method="corr" (wc_fcd; Hansen et al. 2015): sliding windows of `window` samples every `step`
+    (default 1), nw = (M - window) // step + 1 of them; FC_k = np.corrcoef of window k, its pattern the
+    strict upper triangle (utils.flat_FC's order, P = N (N - 1) / 2 entries); fcd[b][k][l] the Pearson
+    correlation of patterns k and l -> fcd [B][nw][nw] ([nw][nw] for 2-D input), exactly symmetric
+    with a unit diagonal; with want_windows also the patterns, (fcd, windows [B][nw][P]).  A column
+    that is constant within a window makes row and column k of fcd NaN, nothing else.  3 <= N <= 96,
+    2 <= window <= M, nw <= FCD_MAX_WINDOWS = 4096.  ws_bytes: workspace size (default: what all B
+    simulations want, at most FCD_WS_CAP, never below the minimum, 8 simulations' patterns); the result
+    does not depend on it.
+
+    method="phase" (wc_fcd_phase; Deco & Kringelbach 2016): x must be band-limited already; from
+    hilbert_phase's phasors, less `trim` samples at either end (the transform's edge effects),
+    d_t[i][j] = cos(theta_i(t) - theta_j(t)) and fcd[b][t][u] the cosine similarity of the strict upper
+    triangles of d_t and d_u -> [B][M - 2 trim][M - 2 trim].  2 <= N <= 96, M - 2 trim <=
+    FCD_PHASE_MAX_M = 4096.  window and step have no meaning here and must be left None."""
+    if method not in FCD_METHODS:
+        raise ValueError(f"fcd: unknown method {method!r}, must be one of {list(FCD_METHODS)}")
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.float64 or x.dim() not in (2, 3):
+        raise TypeError("fcd: x must be a [M][C] or [M][B][N] fp64 device tensor")
+    single = x.dim() == 2
+    M, B, N = x.shape[0], (1 if single else x.shape[1]), x.shape[-1]
+    if B < 1 or N > FCD_MAX_N:
+        raise ValueError(f"fcd: N = {N}, B = {B}: needs B >= 1 and N <= {FCD_MAX_N} (one window's correlation "
+                         "matrix, a tile's phasors per workgroup)")
+    L = _lib.lib()
+    if method == "phase":
+        if window is not None or step is not None:
+            raise ValueError("fcd: method='phase' has no windows: window and step must be left None")
+        if want_windows or ws_bytes is not None:
+            raise ValueError("fcd: method='phase' takes neither want_windows nor ws_bytes")
+        trim = int(trim)
+        Mt = M - 2 * trim
+        if trim < 0 or N < 2 or M < 2 or Mt < 1 or Mt > FCD_PHASE_MAX_M:
+            raise ValueError(f"fcd: method='phase' needs N >= 2, trim >= 0 and 1 <= M - 2 trim <= {FCD_PHASE_MAX_M} "
+                             f"(N = {N}, M = {M}, trim = {trim})")
+        ph = hilbert_phase(x.reshape(M, B * N).contiguous())[trim:M - trim].view(Mt, B, N, 2)
+        out = fcd_from_phasors(ph)
+        return out[0] if single else out
+    if trim:
+        raise ValueError("fcd: method='corr' takes no trim (it goes with method='phase')")
+    if window is None:
+        raise ValueError("fcd: method='corr' needs a window length")
+    window, step = int(window), (1 if step is None else int(step))
+    if N < 3 or window < 2 or window > M or step < 1:
+        raise ValueError(f"fcd: method='corr' needs N >= 3, 2 <= window <= M and step >= 1 (N = {N}, M = {M}, "
+                         f"window = {window}, step = {step})")
+    nw = (M - window) // step + 1
+    if nw > FCD_MAX_WINDOWS:
+        raise ValueError(f"fcd: {nw} windows > {FCD_MAX_WINDOWS}: take a larger step")
+    P = N * (N - 1) // 2
+    need = L.wc_fcd_workspace_size(B, N, M, window, step)
+    nbytes = max(need, min((nw * P + nw) * 8 * B, FCD_WS_CAP)) if ws_bytes is None else int(ws_bytes)
+    x = x.contiguous()
+    out = torch.empty((B, nw, nw), dtype=torch.float64, device=x.device)
+    pats = torch.empty((B, nw, P), dtype=torch.float64, device=x.device) if want_windows else None
+    ws = torch.empty((max(nbytes, 8) + 7) // 8, dtype=torch.float64, device=x.device)
+    _lib.check(L.wc_fcd(B, N, M, _lib.ptr(x), window, step, _lib.ptr(out), _lib.ptr(pats), _lib.ptr(ws), nbytes,
+                        _lib.stream_handle()), "wc_fcd")
+    if single:
+        out, pats = out[0], (pats[0] if want_windows else None)
+    return (out, pats) if want_windows else out
+
+
+def fcd_from_phasors(phasor):
+    """The phase-coherence FCD (wc_fcd_phase) of unit phasors the caller already holds: phasor
+    [M][C][2] or [M][B][N][2] fp64 (hilbert_phase's output, trimmed as wanted) -> [M][M] or [B][M][M];
+    see fcd(method="phase").  2 <= N <= 96, M <= FCD_PHASE_MAX_M = 4096."""
+    if not isinstance(phasor, torch.Tensor) or phasor.dtype != torch.float64 or phasor.dim() not in (3, 4) \
+            or phasor.shape[-1] != 2:
+        raise TypeError("fcd_from_phasors: phasor must be a [M][C][2] or [M][B][N][2] fp64 device tensor")
+    single = phasor.dim() == 3
+    M, B, N = phasor.shape[0], (1 if single else phasor.shape[1]), phasor.shape[-2]
+    if B < 1 or N < 2 or N > FCD_MAX_N or M < 1 or M > FCD_PHASE_MAX_M:
+        raise ValueError(f"fcd_from_phasors: N = {N}, B = {B}, M = {M}: needs B >= 1, 2 <= N <= {FCD_MAX_N} and "
+                         f"1 <= M <= {FCD_PHASE_MAX_M}")
+    phasor = phasor.contiguous()
+    out = torch.empty((B, M, M), dtype=torch.float64, device=phasor.device)
+    _lib.check(_lib.lib().wc_fcd_phase(B, N, M, _lib.ptr(phasor), _lib.ptr(out), _lib.stream_handle()),
+               "wc_fcd_phase")
+    return out[0] if single else out
+
+
+FCD_KS_CHUNK = 256        # fcd_ks: simulations a pass (bounds the sorted copies)
+
+
+def fcd_ks(fcd, emp_values, lag=1):
+    """Two-sample Kolmogorov-Smirnov statistic, per simulation, between the entries fcd[b][k][l] with
+    l - k >= lag and the 1-D sample emp_values (an empirical FCD's entries): the usual distance a sweep is
+    fitted on.  fcd [B][nw][nw] or [nw][nw] fp64 device tensor -> [B] (a scalar tensor for one matrix);
+    a simulation with a NaN among its selected entries gets NaN.  Plain torch (sort, searchsorted) on the
+    device, FCD_KS_CHUNK simulations at a time."""
+    if not isinstance(fcd, torch.Tensor) or fcd.dtype != torch.float64 or fcd.dim() not in (2, 3) \
+            or fcd.shape[-1] != fcd.shape[-2]:
+        raise TypeError("fcd_ks: fcd must be a [B][nw][nw] or [nw][nw] fp64 device tensor")
+    single = fcd.dim() == 2
+    f = fcd[None] if single else fcd
+    nw, lag = f.shape[-1], int(lag)
+    if lag < 1 or lag >= nw:
+        raise ValueError(f"fcd_ks: lag = {lag} must be in 1 .. nw - 1 = {nw - 1}")
+    emp = torch.as_tensor(np.asarray(emp_values.cpu() if isinstance(emp_values, torch.Tensor) else emp_values,
+                                     dtype=np.float64))
+    if emp.dim() != 1 or emp.numel() == 0 or bool(torch.isnan(emp).any()):
+        raise ValueError("fcd_ks: emp_values must be a 1-D sample without NaN, not empty")
+    emp = emp.to(f.device).sort().values
+    mask = torch.ones((nw, nw), dtype=torch.bool, device=f.device).triu(lag)
+    na, ne = int(mask.sum()), emp.numel()
+    out = torch.empty(f.shape[0], dtype=torch.float64, device=f.device)
+    for b0 in range(0, f.shape[0], FCD_KS_CHUNK):
+        a = f[b0:b0 + FCD_KS_CHUNK][:, mask]                   # [b][na]
+        bad = torch.isnan(a).any(dim=1)
+        a = a.nan_to_num(nan=0.0).sort(dim=1).values
+        pooled = torch.cat((a, emp.expand(a.shape[0], ne)), dim=1).contiguous()
+        cdf_a = torch.searchsorted(a, pooled, right=True).double() / na
+        cdf_e = torch.searchsorted(emp, pooled, right=True).double() / ne
+        d = (cdf_a - cdf_e).abs().amax(dim=1)
+        out[b0:b0 + FCD_KS_CHUNK] = torch.where(bad, torch.full_like(d, float("nan")), d)
+    return out[0] if single else out
 
 
 def welch_peak(E_t, fs=500.0, want_psd=False):

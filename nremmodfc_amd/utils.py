@@ -269,6 +269,27 @@ def connectivity(series, dt=0.002, freqs=[8, 13], measures=("plv", "pli", "wpli"
     return {m: v.cpu().numpy() for m, v in sigchain.phase_connectivity(xt, names).items()}
 
 
+def fcd(series, window=30, step=1, method="corr", trim=0, device="cuda"):
+    """Functional connectivity dynamics of series (time, rois) or (time, B, N) on the device
+    (sigchain.fcd).  method="corr": the correlations between the FC patterns of sliding windows of
+    `window` samples every `step` -> (nw, nw) or (B, nw, nw), nw = (time - window) // step + 1.
+    method="phase": the cosine similarities between the instantaneous phase-coherence patterns of an
+    already band-limited series, less `trim` samples at either end -> (time - 2 trim, time - 2 trim)
+    or with a leading B; window and step are not used.  numpy in (float32 accepted), numpy out.
+    3 <= N <= 96 (phase: 2), nw and time - 2 trim <= 4096."""
+    x = np.asarray(series)
+    if x.dtype.kind not in "fiub":
+        raise TypeError(f"fcd: series must be real numbers, not {x.dtype}")
+    if x.ndim not in (2, 3) or x.size == 0:
+        raise ValueError("series must be (time, rois) or (time, B, N)")
+    if method not in sigchain.FCD_METHODS:
+        raise ValueError(f"fcd: unknown method {method!r}, must be one of {list(sigchain.FCD_METHODS)}")
+    xt = torch.from_numpy(np.array(x, dtype=np.float64, order="C")).to(device)
+    if method == "phase":
+        return sigchain.fcd(xt, method="phase", trim=trim).cpu().numpy()
+    return sigchain.fcd(xt, window, step).cpu().numpy()
+
+
 def kuramoto(sign):
     """utils.py:34-40: (sync, meta) of the Kuramoto order parameter of sign (T x N)
     from the phases of its analytic signal (hilbert along axis 0).
