@@ -188,7 +188,11 @@ int wc_bold_finish(const wc_bold_cfg* cfg, int64_t C, const double* state, doubl
  * (Balance), hin_node[B][N], hse_node[B][N] (nodal_measures); optional
  * clus_num [B][N-1] int32 (Functional_HP's Clus_num) and sv [B][N] (singular
  * values of the symmetrised positive part, descending).  Eigen-decomposition
- * by cyclic Jacobi in LDS, one workgroup per matrix. */
+ * by cyclic Jacobi in LDS, one workgroup per matrix.
+ * Non-finite entries: the clip comes first, so -Inf becomes 0 and a NaN stays.  A
+ * matrix that then holds a NaN or +Inf gets NaN in hin, hse, hin_node, hse_node
+ * and sv and -1 in every clus_num; its NaN and +Inf entries stay in fc.  The other
+ * matrices of the batch are not affected. */
 int wc_hma(int B, int N, double* fc, double* hin, double* hse, double* hin_node, double* hse_node,
            int* clus_num, double* sv, void* stream);
 
@@ -198,7 +202,10 @@ int wc_hma(int B, int N, double* fc, double* hin, double* hse, double* hin_node,
  * j the eigenvector of lam[j].  Ranks |lam| (stable, descending), walks the
  * levels (HMA.py:62-101), Balance and nodal_measures as wc_hma.  N <= 4096
  * (the label arrays take 40 B per node of the 160 KB LDS; larger N returns
- * WC_EUNSUPPORTED). */
+ * WC_EUNSUPPORTED).  A matrix with a NaN or infinite value in lam gets NaN in
+ * every floating output and -1 in every clus_num, without a ranking (vt is not
+ * read): a caller marks a matrix that is not finite this way and keeps it from
+ * its eigensolver. */
 int wc_hma_modes(int B, int N, const double* lam, const double* vt, double* hin, double* hse,
                  double* hin_node, double* hse_node, int* clus_num, double* sv, void* stream);
 
@@ -245,7 +252,10 @@ int wc_filtfilt(int order, const double* b, const double* a, const double* zi, i
  * (utils.kuramoto, utils.py:35-37): phasor [M][C][2] (cos, sin).  workspace:
  * >= M doubles.  Range: 2 <= M <= 8192.  It is a direct circulant convolution,
  * O(M^2) per column, with the length-M Hilbert kernel in LDS (M * 8 bytes of a
- * 64 KB launch); longer series return WC_EUNSUPPORTED: use wc_hilbert_phase_long. */
+ * 64 KB launch); longer series return WC_EUNSUPPORTED: use wc_hilbert_phase_long.
+ * A sample whose analytic signal is exactly 0 has the phasor (1, 0) (numpy's
+ * angle(0) = 0).  A NaN or infinite sample makes phasors of its column NaN (every
+ * one of them for a NaN), never (1, 0), and touches no other column. */
 int wc_hilbert_phase(int64_t C, int M, const double* x, double* phasor, void* workspace,
                      size_t ws_bytes, void* stream);
 
@@ -257,7 +267,8 @@ int wc_hilbert_phase(int64_t C, int M, const double* x, double* phasor, void* wo
  * and its spectrum) and two [L] complex buffers for one column; every further
  * 32 L bytes let one more column be in flight per pass (up to C), and the result
  * is bit-identical for every workspace size and every C.  0 for C <= 0, M < 2 or
- * M > 524288 (wc_hilbert_phase_long then returns WC_EINVAL / WC_EUNSUPPORTED). */
+ * M > 524288 (wc_hilbert_phase_long then returns WC_EINVAL / WC_EUNSUPPORTED).
+ * Zero, NaN and infinite samples as wc_hilbert_phase. */
 size_t wc_hilbert_long_workspace_size(int64_t C, int64_t M);
 int wc_hilbert_phase_long(int64_t C, int64_t M, const double* x, double* phasor, void* workspace,
                           size_t ws_bytes, void* stream);
@@ -285,7 +296,12 @@ int wc_hilbert_envelope(int64_t C, int64_t M, const double* x, double* env, int 
  * LDS, no workspace (may be NULL).  N > 96 (config 5, N = 1000): the FC is tiled
  * through global memory (wc_fc_large.hip) and workspace must hold
  * wc_fc_metrics_workspace_size(B, N, M, K, fc_out != NULL) bytes (it includes
- * the B N^2 doubles of FC when fc_out is NULL).  Deterministic for every N. */
+ * the B N^2 doubles of FC when fc_out is NULL).  Deterministic for every N.
+ * Non-finite values, as numpy: a constant column (0 / 0), a NaN
+ * or an infinite sample make that column's row and column of the FC NaN, diagonal
+ * included; an FC with a NaN (fc_in too) gives NaN in mean(sFC) and in the
+ * metrics that read it; NaN phasors give NaN sync and meta.  The other
+ * simulations of the batch are not affected. */
 size_t wc_fc_metrics_workspace_size(int B, int N, int M, int K, int want_fc);
 int wc_fc_metrics(int B, int N, int M, const double* bold, const double* fc_in, const double* empfc,
                   int K, double data_range, const double* phasor, double* fc_out, double* metrics,
@@ -294,7 +310,8 @@ int wc_fc_metrics(int B, int N, int M, const double* bold, const double* fc_in, 
 /* np.corrcoef(x[:, b, :].T) for every simulation b of a long time-major series
  * x [M][B][N] (the SC optimiser's FC, optimize_SC_Hopf.py:67-69: 6000 samples),
  * split over time blocks so a small batch still fills the GPU; fc [B][N][N],
- * clipped to [-1, 1].  N >= 2, M >= 2 (N > 96: 64 x 64 covariance tiles in
+ * clipped to [-1, 1] (a NaN stays: a constant column, a NaN or an infinite sample
+ * make that column's row and column NaN, as numpy).  N >= 2, M >= 2 (N > 96: 64 x 64 covariance tiles in
  * global memory, wc_fc_large.hip).  Deterministic (fixed blocks, fixed combine
  * order).  workspace: wc_corrcoef_workspace_size(B, N, M) bytes. */
 size_t wc_corrcoef_workspace_size(int B, int N, int M);
@@ -302,7 +319,8 @@ int wc_corrcoef(int B, int N, int M, const double* x, double* fc, void* workspac
                 void* stream);
 
 /* utils.kuramoto (utils.py:34-40) from unit phasors [M][B][N][2] (wc_hilbert_phase):
- * out [B][2] = (mean_t R(t), std_t R(t)), R(t) = |mean_n exp(i theta_n(t))|. */
+ * out [B][2] = (mean_t R(t), std_t R(t)), R(t) = |mean_n exp(i theta_n(t))|; NaN
+ * for a simulation with a NaN phasor. */
 int wc_kuramoto(int B, int N, int M, const double* phasor, double* out, void* stream);
 
 /* ------------------------------------------------------------------------

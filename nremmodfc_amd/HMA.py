@@ -95,7 +95,10 @@ def integration_segregation_batch(sfcs, device="cuda"):
     wc_hma_modes launch (sigchain.hma).
 
     Returns one dict per matrix with the keys run_many_seeds.py:134-136 pickles;
-    sFC is the clipped matrix (as the reference saves it).
+    sFC is the clipped matrix (as the reference saves it).  A matrix that holds a NaN
+    or +Inf after the clip gets NaN values (the per-matrix functions above raise
+    LinAlgError on it, as the reference's SVD does) and keeps those entries in sFC;
+    the other matrices of the batch are not affected.
     """
     import torch
 

@@ -15,6 +15,9 @@ inline int wc_set_err(int code, const char* msg) {
     return code;
 }
 inline void wc_clear_err() { wc_errbuf()[0] = 0; }
+
+// np.clip(v, -1, 1): a NaN stays a NaN (fmin / fmax would return the bound)
+__device__ __forceinline__ double clip1(double v) { return v > 1.0 ? 1.0 : (v < -1.0 ? -1.0 : v); }
 inline int wc_hip_check(const char* what) {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {

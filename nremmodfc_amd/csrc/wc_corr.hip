@@ -161,12 +161,12 @@ __global__ void __launch_bounds__(128) corr_row_kernel(int N, int M, int nblk, c
         for (int q = 0; q < nblk; ++q) s += cb[q * NN + j];
         double v = (s * fact) / sdb[i];
         v = v / sdb[j];
-        v = fmin(1.0, fmax(-1.0, v));
+        v = clip1(v);
         fc[(int64_t)b * NN + (int64_t)i * N + j] = v;
         if (j != i) {  // np.corrcoef: c[j][i] / sd_j / sd_i (division order as numpy, not mirrored bits)
             double w = (s * fact) / sdb[j];
             w = w / sdb[i];
-            fc[(int64_t)b * NN + (int64_t)j * N + i] = fmin(1.0, fmax(-1.0, w));
+            fc[(int64_t)b * NN + (int64_t)j * N + i] = clip1(w);
         }
     }
 }

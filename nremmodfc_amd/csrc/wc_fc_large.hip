@@ -158,11 +158,11 @@ __global__ void __launch_bounds__(128) corr_norm_kernel(int N, const double* __r
         const double c = f[(int64_t)i * N + j];
         double v = c / si;
         v = v / s[j];
-        f[(int64_t)i * N + j] = fmin(1.0, fmax(-1.0, v));
+        f[(int64_t)i * N + j] = clip1(v);
         if (j != i) {
             double w = c / s[j];
             w = w / si;
-            f[(int64_t)j * N + i] = fmin(1.0, fmax(-1.0, w));
+            f[(int64_t)j * N + i] = clip1(w);
         }
     }
 }
@@ -302,7 +302,7 @@ __global__ void gof_final_kernel(int B, int N, int K, int nbands, const double* 
         const double my = sy / nflat;
         const double f1 = 1.0 / (nflat - 1);
         double corr = (s[2] * f1) / sqrt(s[0] * f1) / sqrt(s[1] * f1);
-        corr = fmin(1.0, fmax(-1.0, corr));
+        corr = clip1(corr);
         double* o = metrics + ((int64_t)b * K + k) * 4;
         o[0] = corr;
         o[1] = sqrt(s[3]);

@@ -45,9 +45,6 @@ constexpr int kPhaseTile = 32; // side of a tile of fcd_phase (2 x 2 cells a thr
 constexpr int kPhaseNc = 32;   // nodes of a tile's times in LDS at a time
 constexpr int kMinSims = 8;    // simulations in flight that the minimum workspace holds
 
-// np.clip(v, -1, 1): a NaN stays a NaN
-__device__ __forceinline__ double clip1(double v) { return v > 1.0 ? 1.0 : (v < -1.0 ? -1.0 : v); }
-
 // a norm that a correlation can be divided by: not 0, not NaN, not infinite
 __device__ __forceinline__ bool usable(double n) { return n > 0.0 && n < INFINITY; }
 

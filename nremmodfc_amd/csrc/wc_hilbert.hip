@@ -119,7 +119,8 @@ __global__ void __launch_bounds__(kThreads) hl_col_kernel(const HlArgs a) {
                     a.ph[n * a.C + a.c0 + c] = r / (double)a.M;
                 } else {
                     d2* o = reinterpret_cast<d2*>(a.ph) + n * a.C + a.c0 + c;
-                    *o = r > 0 ? d2{s.x / r, s.y / r} : d2{1.0, 0.0};  // numpy: angle(0) = 0
+                    // numpy: angle(0) = 0; a NaN modulus is not 0 and gives a NaN phasor
+                    *o = r == 0 ? d2{1.0, 0.0} : d2{s.x / r, s.y / r};
                 }
             }
         }

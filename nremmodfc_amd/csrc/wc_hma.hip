@@ -21,6 +21,10 @@
 // off-diagonal mass is below 1e-30 of the total.  Then the ranks of |lambda|
 // (stable descending, as LAPACK's ordering), the level-by-level module labels
 // (label <- 2 label + [u_m >= 0], compacted; HMA.py:62-101) and the sums.
+//
+// Non-finite entries: the clip comes first (-Inf -> 0, a NaN stays); a
+// matrix that then holds a NaN or +Inf gets NaN outputs and -1 module counts.  Both
+// kernels find it before the ranking: the ranks index LDS, V and global memory.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -32,6 +36,23 @@ constexpr int kMaxN = 96;
 constexpr int kThreads = 256;
 constexpr int kMaxSweeps = 30;
 
+// the outputs of a matrix that holds a NaN or +Inf after the clip (or whose spectrum is not finite):
+// NaN, and -1 module counts, the graph kernels' convention
+__device__ void hma_write_nan(int N, int tid, size_t b, double* __restrict__ hin, double* __restrict__ hse,
+                              double* __restrict__ hin_node, double* __restrict__ hse_node,
+                              int* __restrict__ clus_num, double* __restrict__ sv_out) {
+    if (tid == 0) {
+        hin[b] = NAN;
+        hse[b] = NAN;
+    }
+    for (int k = tid; k < N; k += kThreads) {
+        hin_node[b * N + k] = NAN;
+        hse_node[b * N + k] = NAN;
+        if (sv_out) sv_out[b * N + k] = NAN;
+        if (clus_num && k < N - 1) clus_num[b * (N - 1) + k] = -1;
+    }
+}
+
 __global__ void __launch_bounds__(kThreads) hma_kernel(int N, double* __restrict__ fc, double* __restrict__ hin,
                                                        double* __restrict__ hse, double* __restrict__ hin_node,
                                                        double* __restrict__ hse_node, int* __restrict__ clus_num,
@@ -41,7 +62,7 @@ __global__ void __launch_bounds__(kThreads) hma_kernel(int N, double* __restrict
     const int P = Np / 2;
     double* A = lds;              // [Np][Np]
     double* V = A + Np * Np;      // [Np][Np], V[k][j] = component k of eigenvector j
-    double* cs = V + Np * Np;     // [P][2] (c, s) of this round
+    double* cs = V + Np * Np;     // [P][2] (s, tau) of this round
     double* lam = cs + 2 * P;     // [Np] eigenvalues
     double* red = lam + Np;       // [kThreads] reduction scratch
     double* hf = red + kThreads;  // [Np] HF (HMA.py:141)
@@ -53,22 +74,45 @@ __global__ void __launch_bounds__(kThreads) hma_kernel(int N, double* __restrict
     const int tid = threadIdx.x;
     double* F = fc + (size_t)blockIdx.x * N * N;
 
-    // ---- F = (max(FC, 0) + max(FC, 0)^T) / 2, and the in-place clip of the caller's FC (HMA.py:55) ----
+    // ---- F = (clip(FC) + clip(FC)^T) / 2, and the in-place clip of the caller's FC (HMA.py:55) ----
+    // the clip is FC[FC < 0] = 0: -Inf becomes 0, a NaN stays a NaN (fmax would make it 0)
+    int nonfinite = 0;
     for (int i = tid; i < Np * Np; i += kThreads) {
         const int r = i / Np, c = i % Np;
         double x = 0.0;
         if (r < N && c < N) {
-            const double a = fmax(F[r * N + c], 0.0), b = fmax(F[c * N + r], 0.0);
+            const double fa = F[r * N + c], fb = F[c * N + r];
+            const double a = fa < 0 ? 0.0 : fa, b = fb < 0 ? 0.0 : fb;
             x = (a + b) / 2;
         }
+        nonfinite |= !(fabs(x) < INFINITY);
         A[i] = x;
         V[i] = r == c ? 1.0 : 0.0;
     }
-    __syncthreads();
+    nonfinite = __syncthreads_or(nonfinite);  // uniform
     for (int i = tid; i < N * N; i += kThreads)
         if (F[i] < 0) F[i] = 0.0;  // every thread reads F before any writes it (barrier above)
+    // a NaN or +Inf left after the clip: NaN in every output, -1 in clus_num, and no ranking
+    if (nonfinite) {
+        hma_write_nan(N, tid, blockIdx.x, hin, hse, hin_node, hse_node, clus_num, sv_out);
+        return;
+    }
 
     // ---- cyclic Jacobi, round-robin ordering ----
+    // Rutishauser's form of the rotation (Numerical Recipes' jacobi): with t = tan, s = sin and
+    // tau = s / (1 + c), the pair's diagonal moves by h = t a_pq (a_pp -= h, a_qq += h, a_pq = 0
+    // exactly) and every other entry by a small correction to itself, g - s (h + g tau) and
+    // h + s (g - h tau), instead of c g - s h.  The h of a sweep are summed apart (zs) and added to the
+    // diagonal of the sweep's start (ds) once, at its end: an eigenvalue takes one rounding of its own
+    // size per sweep, not five per rotation, which kept wc_hma's eigenvalues 20 to 90 ulp from a
+    // 40-digit reference where LAPACK's are within a few.
+    double* zs = lam;  // [Np] sum of the sweep's h per diagonal entry (lam and hf are free until the ranking)
+    double* ds = hf;   // [Np] diagonal at the start of the sweep
+    for (int i = tid; i < Np; i += kThreads) {
+        zs[i] = 0.0;
+        ds[i] = A[i * Np + i];
+    }
+    __syncthreads();
     for (int sweep = 0; sweep < kMaxSweeps; ++sweep) {
         // convergence: off-diagonal mass vs total (one reduction per sweep)
         double off = 0.0, tot = 0.0;
@@ -103,16 +147,25 @@ __global__ void __launch_bounds__(kThreads) hma_kernel(int N, double* __restrict
                 int q = k == 0 ? m : (rnd - k + m) % m;
                 if (p > q) { const int t = p; p = q; q = t; }
                 const double apq = A[p * Np + q];
-                double c = 1.0, s = 0.0;
+                double s = 0.0, tau = 0.0;
                 if (apq != 0.0) {
                     const double app = A[p * Np + p], aqq = A[q * Np + q];
                     const double th = (aqq - app) / (2.0 * apq);
                     const double t = (th >= 0 ? 1.0 : -1.0) / (fabs(th) + sqrt(fma(th, th, 1.0)));
-                    c = 1.0 / sqrt(fma(t, t, 1.0));
+                    const double c = 1.0 / sqrt(fma(t, t, 1.0));
                     s = t * c;
+                    tau = s / (1.0 + c);
+                    // the pair's 2 x 2 block, which the two passes below leave alone
+                    const double h = t * apq;
+                    zs[p] -= h;
+                    zs[q] += h;
+                    A[p * Np + p] = app - h;
+                    A[q * Np + q] = aqq + h;
+                    A[p * Np + q] = 0.0;
+                    A[q * Np + p] = 0.0;
                 }
-                cs[2 * k] = c;
-                cs[2 * k + 1] = s;
+                cs[2 * k] = s;
+                cs[2 * k + 1] = tau;
             }
             __syncthreads();
             // columns p, q of A and V: A <- A J, V <- V J
@@ -121,13 +174,16 @@ __global__ void __launch_bounds__(kThreads) hma_kernel(int N, double* __restrict
                 int p = k == 0 ? rnd : (rnd + k) % m;
                 int q = k == 0 ? m : (rnd - k + m) % m;
                 if (p > q) { const int t = p; p = q; q = t; }
-                const double c = cs[2 * k], s = cs[2 * k + 1];
+                const double s = cs[2 * k], tau = cs[2 * k + 1];
+                // branch-free (one wave per SIMD: the loads of several iterations must overlap); the
+                // pair's own block keeps what the pair's thread wrote, and s = 0 changes nothing
+                const bool own = row == p || row == q;
                 const double ap = A[row * Np + p], aq = A[row * Np + q];
-                A[row * Np + p] = c * ap - s * aq;
-                A[row * Np + q] = s * ap + c * aq;
+                A[row * Np + p] = own ? ap : ap - s * (aq + ap * tau);
+                A[row * Np + q] = own ? aq : aq + s * (ap - aq * tau);
                 const double vp = V[row * Np + p], vq = V[row * Np + q];
-                V[row * Np + p] = c * vp - s * vq;
-                V[row * Np + q] = s * vp + c * vq;
+                V[row * Np + p] = vp - s * (vq + vp * tau);
+                V[row * Np + q] = vq + s * (vp - vq * tau);
             }
             __syncthreads();
             // rows p, q of A: A <- J^T A
@@ -136,18 +192,37 @@ __global__ void __launch_bounds__(kThreads) hma_kernel(int N, double* __restrict
                 int p = k == 0 ? rnd : (rnd + k) % m;
                 int q = k == 0 ? m : (rnd - k + m) % m;
                 if (p > q) { const int t = p; p = q; q = t; }
-                const double c = cs[2 * k], s = cs[2 * k + 1];
+                const double s = cs[2 * k], tau = cs[2 * k + 1];
+                const bool own = col == p || col == q;
                 const double ap = A[p * Np + col], aq = A[q * Np + col];
-                A[p * Np + col] = c * ap - s * aq;
-                A[q * Np + col] = s * ap + c * aq;
+                A[p * Np + col] = own ? ap : ap - s * (aq + ap * tau);
+                A[q * Np + col] = own ? aq : aq + s * (ap - aq * tau);
             }
             __syncthreads();
         }
+        // the sweep's diagonal: its start plus the summed h
+        for (int i = tid; i < Np; i += kThreads) {
+            ds[i] += zs[i];
+            A[i * Np + i] = ds[i];
+            zs[i] = 0.0;
+        }
+        __syncthreads();
     }
 
     // ---- singular values = |lambda|, ranked descending (stable in the index); the pad is last ----
-    for (int i = tid; i < Np; i += kThreads) lam[i] = i < N ? fabs(A[i * Np + i]) : -1.0;
-    __syncthreads();
+    // the ranks below index LDS and V: they are taken from a finite spectrum only (finite entries whose
+    // sum or squares overflow can still leave a NaN here)
+    nonfinite = 0;
+    for (int i = tid; i < Np; i += kThreads) {
+        const double l = i < N ? fabs(A[i * Np + i]) : -1.0;
+        nonfinite |= !(l < INFINITY);
+        lam[i] = l;
+    }
+    nonfinite = __syncthreads_or(nonfinite);
+    if (nonfinite) {
+        hma_write_nan(N, tid, blockIdx.x, hin, hse, hin_node, hse_node, clus_num, sv_out);
+        return;
+    }
     for (int i = tid; i < Np; i += kThreads) {
         const double li = lam[i];
         int r = 0;
@@ -259,8 +334,19 @@ __global__ void __launch_bounds__(kThreads) hma_modes_kernel(int N, const double
     const int tid = threadIdx.x;
     const size_t b = blockIdx.x;
     const double* vt = vt_all + b * (size_t)N * N;
-    for (int i = tid; i < N; i += kThreads) lam[i] = fabs(lam_in[b * N + i]);
-    __syncthreads();
+    // a NaN or infinite eigenvalue (the caller marks a matrix that is not finite this way): NaN in
+    // every output, -1 in clus_num; the ranks below, which index vt, need a finite spectrum
+    int nonfinite = 0;
+    for (int i = tid; i < N; i += kThreads) {
+        const double l = fabs(lam_in[b * N + i]);
+        nonfinite |= !(l < INFINITY);
+        lam[i] = l;
+    }
+    nonfinite = __syncthreads_or(nonfinite);  // uniform
+    if (nonfinite) {
+        hma_write_nan(N, tid, b, hin, hse, hin_node, hse_node, clus_num, sv_out);
+        return;
+    }
     for (int i = tid; i < N; i += kThreads) {
         const double li = lam[i];
         int r = 0;

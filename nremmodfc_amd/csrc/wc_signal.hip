@@ -624,8 +624,9 @@ __global__ void __launch_bounds__(256) hilbert_phase_kernel(int64_t C, int M, co
                 if constexpr (ENV) {
                     ph[(int64_t)t * C + c] = r;
                 } else {
-                    ph[((int64_t)t * C + c) * 2] = r > 0 ? re / r : 1.0;  // numpy: angle(0) = 0
-                    ph[((int64_t)t * C + c) * 2 + 1] = r > 0 ? acc[k] / r : 0.0;
+                    // numpy: angle(0) = 0; a NaN modulus is not 0 and gives a NaN phasor
+                    ph[((int64_t)t * C + c) * 2] = r == 0 ? 1.0 : re / r;
+                    ph[((int64_t)t * C + c) * 2 + 1] = r == 0 ? 0.0 : acc[k] / r;
                 }
             }
         }
@@ -813,7 +814,7 @@ __global__ void __launch_bounds__(kFcThreads) fc_metrics_kernel(const FcArgs a) 
         const int r = i / N, q = i % N;
         double v = fc[i] / sd[r];
         v = v / sd[q];
-        fc[i] = fmin(1.0, fmax(-1.0, v));
+        fc[i] = clip1(v);
     }
     __syncthreads();
     }
@@ -855,7 +856,7 @@ __global__ void __launch_bounds__(kFcThreads) fc_metrics_kernel(const FcArgs a) 
         see = block_sum(see, red);
         const double f1 = 1.0 / (nflat - 1);
         double corr = (sxy * f1) / sqrt(sxx * f1) / sqrt(syy * f1);
-        corr = fmin(1.0, fmax(-1.0, corr));
+        corr = clip1(corr);
         const double euc = sqrt(see);
         const double newm = 1.0 - corr + (mx - my) * (mx - my);
         // SSIM (skimage 0.18 defaults): 7x7 uniform filter of x, y, xx, yy, xy

@@ -243,6 +243,8 @@ def hma(fc, want_clus_num=False):
     fc [B][N][N] (or [N][N]) fp64 device tensor, clipped in place (FC < 0 -> 0,
     as HMA.py:55).  Returns a dict of device tensors: hin [B], hse [B],
     hin_node [B][N], hse_node [B][N], sv [B][N] (+ clus_num [B][N-1] int32).
+    A matrix that holds a NaN or +Inf after the clip has NaN in all of them (clus_num:
+    -1) and keeps those entries; the other matrices of the batch are not affected.
     """
     L = _lib.lib()
     if fc.dim() == 2:
@@ -264,11 +266,16 @@ def hma(fc, want_clus_num=False):
     # N > 96: F and V no longer fit one workgroup's LDS.  The eigensystem of the symmetrised
     # positive part comes from the batched device eigensolver (rocSOLVER through torch.linalg.eigh),
     # everything after it -- ranks, module levels, Balance, nodal measures -- from wc_hma_modes.
-    fc.clamp_(min=0.0)  # HMA.py:55: the caller's FC is clipped in place
+    fc.clamp_(min=0.0)  # HMA.py:55: the caller's FC is clipped in place (-Inf -> 0, a NaN stays)
     for b0 in range(0, B, HMA_EIGH_BATCH):
         b1 = min(B, b0 + HMA_EIGH_BATCH)
         f = fc[b0:b1]
-        lam, V = torch.linalg.eigh((f + f.transpose(1, 2)) / 2)
+        sym = (f + f.transpose(1, 2)) / 2
+        # a matrix that holds a NaN or +Inf never reaches the eigensolver (it raises for the whole batch or
+        # returns what it likes): zeros go in its place, and a NaN spectrum tells wc_hma_modes to write NaN
+        bad = ~torch.isfinite(sym).all(dim=2).all(dim=1)
+        lam, V = torch.linalg.eigh(torch.where(bad[:, None, None], torch.zeros_like(sym), sym))
+        lam = torch.where(bad[:, None], torch.full_like(lam, float("nan")), lam)
         vt = V.transpose(1, 2).contiguous()  # row j = eigenvector j (coalesced rows per level)
         sl = {k: v[b0:b1] for k, v in out.items()}
         rc = L.wc_hma_modes(b1 - b0, N, _lib.ptr(lam.contiguous()), _lib.ptr(vt), _lib.ptr(sl["hin"]),
