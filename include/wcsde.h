@@ -562,6 +562,66 @@ int wc_fcd(int B, int N, int M, const double* x, int win, int step, double* fcd,
            void* workspace, size_t ws_bytes, void* stream);
 int wc_fcd_phase(int B, int N, int M, const double* phasor, double* fcd, void* stream);
 
+/* LEiDA, Leading Eigenvector Dynamics Analysis (Cabral et al. 2017), and the state statistics a sweep is
+ * fitted on (Deco et al. 2019), in wc_leida.hip.  The reference computes none of it; these definitions
+ * are the contract (tests/leida_reference.py restates them in numpy).  Everything fp64; every
+ * floating-point sum has one fixed order that depends on the shape alone; no floating-point atomics; all
+ * arguments are checked before any device work.  1 <= R <= WC_LEIDA_MAX_ROWS (more: WC_EUNSUPPORTED),
+ * 2 <= N <= 1024 and 1 <= K <= 32 (more: WC_EUNSUPPORTED); pointers not NULL, doubles and int64 8-byte
+ * aligned, int32 4-byte aligned, nothing overlapping.
+ *
+ * wc_leida_eigvec: phasor [R][N][2] fp64, 16-byte aligned: wc_hilbert_phase's [M][B][N][2] seen flat,
+ *   R = M B (unit modulus is not required).  With c = phasor[r][.][0], s = phasor[r][.][1] the phase
+ *   coherence matrix is A = c c^T + s s^T, whose non-zero eigenvalues are those of [[cc, cs], [cs, ss]],
+ *   cc = sum c^2, ss = sum s^2, cs = sum c s: with h = (cc - ss) / 2 and r = hypot(h, cs),
+ *   lambda1,2 = (cc + ss) / 2 +- r, w = (h + r, cs) if h >= 0, else (cs, r - h), and
+ *     vec   [R][N]  v = (w0 c + w1 s) / its norm, negated if p = #{v_i > 0} has 2 p > N, or 2 p = N and
+ *                   sum v > 0 (most entries negative; the sum in the kernel's own order)
+ *     share [R]     lambda1 / (lambda1 + lambda2)
+ *   r = 0 exactly (lambda1 = lambda2): the row of vec NaN, share 0.5, NaN for an all-zero row.  A NaN
+ *   or an infinity in a row, or squares that overflow: that row of vec and its share NaN, nothing else.
+ *   A row's bits depend on that row and N only.
+ *
+ * wc_kmeans_assign: x [R][N], cent [K][N], metric WC_KMEANS_SQEUCLIDEAN: sum (x - c)^2, summed as it
+ *   stands, or WC_KMEANS_COSINE: 1 - x.c / (|x| |c|).
+ *     labels [R] int32  the centroid of smallest distance, a tie to the lowest k
+ *     dist   [R]        that distance
+ *   A row with a NaN or an infinity, or of norm 0 under cosine: label -1, dist NaN.  A centroid with a
+ *   NaN or an infinity, or of norm 0 under cosine, is never chosen; none left: label -1, dist NaN.
+ *
+ * wc_kmeans_update: x [R][N], labels [R] int32, cent_prev [K][N] ->
+ *     cent  [K][N]      the mean of the rows labelled k (cosine: of the rows divided by their norms; a
+ *                       member of norm 0 makes its centroid NaN, as numpy); cent_prev[k] where there are none
+ *     count [K] int64   the rows labelled k
+ *   Labels outside 0 .. K-1 (-1 among them) belong to nobody.  A NaN in a row reaches its own cluster only.
+ *   Workspace: wc_kmeans_workspace_size() bytes (0: bad shape): the partial sums of every block of
+ *   WC_KMEANS_UPDATE_BLOCK rows, K N doubles and K int64 a block, and R norms under cosine; blocks are
+ *   added in index order.  Less: WC_EWORKSPACE; more is never touched, so the bits of cent depend on
+ *   (R, N, K), the metric and the data only.
+ *
+ * wc_state_stats: labels [M][B] int32, time-major (what assigning [M][B][N] eigenvectors yields), K
+ *   states, B >= 1, M >= 1.  With V = the times whose label is in 0 .. K-1,
+ *     occupancy [B][K]     #{t in V: l_t = k} / #V; all NaN if V is empty
+ *     dwell     [B][K]     the mean length in samples of the maximal runs of k (runs that touch either
+ *                          end count; any other label ends a run); NaN if k never occurs
+ *     trans     [B][K][K]  #{t: l_t = i, l_t+1 = j} / #{t: l_t = i, l_t+1 in V}, self-transitions
+ *                          included, rows summing to 1; a row NaN if i has no successor
+ *   counted in integers and divided once.  A label outside -1 .. K-1 counts as -1: the status path for
+ *   device-side findings, wc_integrate_status, reads a word of wc_integrate's workspace, and
+ *   wc_state_stats has none. */
+#define WC_LEIDA_MAX_ROWS ((int64_t)1 << 40)
+#define WC_KMEANS_UPDATE_BLOCK 256  /* wc_kmeans_update: rows of a partial sum */
+enum wc_kmeans_metric { WC_KMEANS_SQEUCLIDEAN = 0, WC_KMEANS_COSINE = 1 };
+int wc_leida_eigvec(int64_t R, int N, const double* phasor, double* vec, double* share, void* stream);
+int wc_kmeans_assign(int64_t R, int N, int K, const double* x, const double* cent, int metric,
+                     int32_t* labels, double* dist, void* stream);
+size_t wc_kmeans_workspace_size(int64_t R, int N, int K, int metric);
+int wc_kmeans_update(int64_t R, int N, int K, const double* x, const int32_t* labels,
+                     const double* cent_prev, int metric, double* cent, int64_t* count, void* workspace,
+                     size_t ws_bytes, void* stream);
+int wc_state_stats(int B, int M, int K, const int32_t* labels, double* occupancy, double* dwell,
+                   double* trans, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -97,6 +97,11 @@ _SIGNATURES = {
     "wc_fcd_workspace_size": (c_sz, [c_int, c_int, c_int, c_int, c_int]),
     "wc_fcd": (c_int, [c_int, c_int, c_int, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "wc_fcd_phase": (c_int, [c_int, c_int, c_int, c_vp, c_vp, c_vp]),
+    "wc_leida_eigvec": (c_int, [c_i64, c_int, c_vp, c_vp, c_vp, c_vp]),
+    "wc_kmeans_assign": (c_int, [c_i64, c_int, c_int, c_vp, c_vp, c_int, c_vp, c_vp, c_vp]),
+    "wc_kmeans_workspace_size": (c_sz, [c_i64, c_int, c_int, c_int]),
+    "wc_kmeans_update": (c_int, [c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "wc_state_stats": (c_int, [c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
 }
 
 

@@ -530,6 +530,226 @@ def fcd_ks(fcd, emp_values, lag=1):
     return out[0] if single else out
 
 
+LEIDA_MAX_N = 1024        # wc_leida_eigvec, wc_kmeans_*: a row in one wave's registers
+KMEANS_MAX_K = 32         # wc_kmeans_*, wc_state_stats
+KMEANS_METRICS = {"sqeuclidean": 0, "cosine": 1}   # WC_KMEANS_SQEUCLIDEAN, WC_KMEANS_COSINE
+KMEANS_UPDATE_BLOCK = 256  # WC_KMEANS_UPDATE_BLOCK: rows of a partial sum of wc_kmeans_update
+
+
+def leida(x, trim=0):
+    """LEiDA's first stage (Cabral et al. 2017) on the device: x [M][C] (one simulation) or [M][B][N] fp64
+    device tensor, time-major and band-limited already.  From hilbert_phase's phasors, less `trim`
+    samples at either end (the transform's edge effects, as fcd(method="phase")), the leading eigenvector
+    of every instantaneous phase-coherence matrix dPC(t)[i][j] = cos(theta_i(t) - theta_j(t))
+    (leida_from_phasors) -> (vec [M - 2 trim][B][N], share [M - 2 trim][B]), without B for 2-D input.
+    2 <= N <= LEIDA_MAX_N = 1024."""
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.float64 or x.dim() not in (2, 3):
+        raise TypeError("leida: x must be a [M][C] or [M][B][N] fp64 device tensor")
+    single = x.dim() == 2
+    M, B, N = x.shape[0], (1 if single else x.shape[1]), x.shape[-1]
+    trim = int(trim)
+    Mt = M - 2 * trim
+    if B < 1 or N < 2 or N > LEIDA_MAX_N or trim < 0 or M < 2 or Mt < 1:
+        raise ValueError(f"leida: needs B >= 1, 2 <= N <= {LEIDA_MAX_N}, trim >= 0, M >= 2 and M - 2 trim >= 1 "
+                         f"(N = {N}, B = {B}, M = {M}, trim = {trim})")
+    ph = hilbert_phase(x.reshape(M, B * N).contiguous())[trim:M - trim]
+    return leida_from_phasors(ph if single else ph.view(Mt, B, N, 2))
+
+
+def leida_from_phasors(phasor):
+    """The leading eigenvector of every phase-coherence matrix (wc_leida_eigvec) of phasors the caller
+    already holds: phasor [M][N][2] or [M][B][N][2] fp64 (hilbert_phase's output, trimmed as wanted; unit
+    modulus is not required) -> (vec, share): vec [M][N] or [M][B][N], unit vectors, most of their
+    entries negative (Cabral's sign rule); share [M] or [M][B] = lambda1 / (lambda1 + lambda2), the part
+    of dPC's variance that the vector carries.  dPC = c c^T + s s^T has rank <= 2, so the vector comes
+    from the closed-form eigenvector of a 2 x 2 Gram matrix: three dot products a row, nothing N x N.
+    A row with lambda1 = lambda2 exactly, or with a NaN or an infinity, is NaN.  2 <= N <= 1024."""
+    if not isinstance(phasor, torch.Tensor) or phasor.dtype != torch.float64 or phasor.dim() not in (3, 4) \
+            or phasor.shape[-1] != 2:
+        raise TypeError("leida_from_phasors: phasor must be a [M][N][2] or [M][B][N][2] fp64 device tensor")
+    N, lead = phasor.shape[-2], tuple(phasor.shape[:-2])
+    R = int(np.prod(lead))
+    if R < 1 or N < 2 or N > LEIDA_MAX_N:
+        raise ValueError(f"leida_from_phasors: N = {N}, {R} rows: needs at least one row and 2 <= N <= {LEIDA_MAX_N}")
+    phasor = phasor.contiguous()
+    if phasor.data_ptr() % 16:
+        phasor = phasor.clone()
+    vec = torch.empty(lead + (N,), dtype=torch.float64, device=phasor.device)
+    share = torch.empty(lead, dtype=torch.float64, device=phasor.device)
+    _lib.check(_lib.lib().wc_leida_eigvec(R, N, _lib.ptr(phasor), _lib.ptr(vec), _lib.ptr(share),
+                                          _lib.stream_handle()), "wc_leida_eigvec")
+    return vec, share
+
+
+def _kmeans_args(name, x, centroids, metric):
+    """What the k-means functions refuse before they touch the device -> (x as [R][N], centroids
+    [K][N], metric code, the leading shape of x)."""
+    if metric not in KMEANS_METRICS:
+        raise ValueError(f"{name}: unknown metric {metric!r}, must be one of {list(KMEANS_METRICS)}")
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.float64 or x.dim() not in (2, 3):
+        raise TypeError(f"{name}: x must be a [R][N] or [M][B][N] fp64 device tensor")
+    if not isinstance(centroids, torch.Tensor) or centroids.dtype != torch.float64 or centroids.dim() != 2:
+        raise TypeError(f"{name}: centroids must be a [K][N] fp64 device tensor")
+    N, K = x.shape[-1], centroids.shape[0]
+    if centroids.shape[1] != N:
+        raise ValueError(f"{name}: centroids have {centroids.shape[1]} nodes, x has N = {N}")
+    if x.numel() == 0 or N < 2 or N > LEIDA_MAX_N:
+        raise ValueError(f"{name}: N = {N}: needs at least one row and 2 <= N <= {LEIDA_MAX_N}")
+    if K < 1 or K > KMEANS_MAX_K:
+        raise ValueError(f"{name}: K = {K}: needs 1 <= K <= {KMEANS_MAX_K}")
+    return x.reshape(-1, N).contiguous(), centroids.contiguous(), KMEANS_METRICS[metric], tuple(x.shape[:-1])
+
+
+def _assign(x2, cent, code):
+    R, N = x2.shape
+    labels = torch.empty(R, dtype=torch.int32, device=x2.device)
+    dist = torch.empty(R, dtype=torch.float64, device=x2.device)
+    _lib.check(_lib.lib().wc_kmeans_assign(R, N, cent.shape[0], _lib.ptr(x2), _lib.ptr(cent), code, _lib.ptr(labels),
+                                           _lib.ptr(dist), _lib.stream_handle()), "wc_kmeans_assign")
+    return labels, dist
+
+
+def _update(x2, labels, cent, code, ws_bytes=None):
+    L = _lib.lib()
+    (R, N), K = x2.shape, cent.shape[0]
+    nbytes = L.wc_kmeans_workspace_size(R, N, K, code) if ws_bytes is None else int(ws_bytes)
+    ws = torch.empty((max(nbytes, 8) + 7) // 8, dtype=torch.float64, device=x2.device)
+    new = torch.empty_like(cent)
+    count = torch.empty(K, dtype=torch.int64, device=x2.device)
+    _lib.check(L.wc_kmeans_update(R, N, K, _lib.ptr(x2), _lib.ptr(labels), _lib.ptr(cent), code, _lib.ptr(new),
+                                  _lib.ptr(count), _lib.ptr(ws), nbytes, _lib.stream_handle()), "wc_kmeans_update")
+    return new, count
+
+
+def kmeans_assign(x, centroids, metric="cosine"):
+    """The nearest centroid of every row (wc_kmeans_assign): x [R][N] or [M][B][N], centroids [K][N], fp64
+    device tensors -> (labels int32, dist), shaped as x without its last axis.  metric "sqeuclidean":
+    sum (x - c)^2; "cosine": 1 - x.c / (|x| |c|).  The smallest distance wins, a tie goes to the lowest
+    k.  A row with a NaN (or an infinity, or without a direction under cosine) gets label -1 and dist NaN;
+    a centroid like that is never chosen.  1 <= K <= 32, 2 <= N <= 1024."""
+    x2, cent, code, lead = _kmeans_args("kmeans_assign", x, centroids, metric)
+    labels, dist = _assign(x2, cent, code)
+    return labels.view(lead), dist.view(lead)
+
+
+def kmeans_update(x, labels, centroids, metric="cosine", ws_bytes=None):
+    """Centroids from labels (wc_kmeans_update): x [R][N] or [M][B][N], labels int32 shaped as x without
+    its last axis, centroids [K][N] the previous ones -> (centroids [K][N], count [K] int64).  Centroid
+    k is the mean of the rows labelled k (cosine: of the rows divided by their norms); rows labelled -1
+    belong to nobody; an empty cluster keeps its previous centroid, count 0.  Partial sums over blocks of
+    KMEANS_UPDATE_BLOCK = 256 rows, added in index order: the bits depend on the shape and the data
+    only, not on ws_bytes (default and minimum: wc_kmeans_workspace_size)."""
+    x2, cent, code, lead = _kmeans_args("kmeans_update", x, centroids, metric)
+    if not isinstance(labels, torch.Tensor) or labels.dtype != torch.int32 or tuple(labels.shape) != lead:
+        raise TypeError("kmeans_update: labels must be an int32 device tensor shaped as x without its last axis")
+    return _update(x2, labels.reshape(-1).contiguous(), cent, code, ws_bytes)
+
+
+def kmeans(x, k_or_init, metric="cosine", max_iter=100, n_init=1, seed=0):
+    """Lloyd's k-means around wc_kmeans_assign and wc_kmeans_update: x [R][N] or [M][B][N] fp64 device
+    tensor (the latter pooled over simulations and times: how empirical states are made) ->
+    (centroids [K][N], labels int32 shaped as x without its last axis, inertia, n_iter).
+
+    k_or_init: initial centroids [K][N], or an integer k: k distinct rows without NaN or infinity,
+    picked by np.random.default_rng(seed); with n_init > 1 as many such draws from the one generator,
+    the run of lowest inertia kept (the first among equals).  Each run: assign; stop if the labels repeat
+    the previous assignment's or after max_iter updates; else update and assign again.  n_iter counts
+    the updates, labels are those of the returned centroids, inertia the sum of their distances over the
+    rows with a label.  No k-means++ seeding, no choice of k."""
+    if isinstance(k_or_init, torch.Tensor):
+        if int(n_init) != 1:
+            raise ValueError("kmeans: explicit initial centroids go with n_init = 1")
+        inits = [k_or_init]
+        x2, _, code, lead = _kmeans_args("kmeans", x, k_or_init, metric)
+    elif not isinstance(k_or_init, (int, np.integer)) or isinstance(k_or_init, bool):
+        raise TypeError("kmeans: k_or_init must be an integer k or initial centroids, a [K][N] fp64 device tensor")
+    else:
+        k = int(k_or_init)
+        if k < 1 or k > KMEANS_MAX_K:
+            raise ValueError(f"kmeans: K = {k}: needs 1 <= K <= {KMEANS_MAX_K}")
+        if int(n_init) < 1:
+            raise ValueError(f"kmeans: n_init = {n_init} < 1")
+        inits = None
+    max_iter = int(max_iter)
+    if max_iter < 0:
+        raise ValueError(f"kmeans: max_iter = {max_iter} < 0")
+    if inits is None:
+        if not isinstance(x, torch.Tensor) or x.dtype != torch.float64 or x.dim() not in (2, 3):
+            raise TypeError("kmeans: x must be a [R][N] or [M][B][N] fp64 device tensor")
+        x2, _, code, lead = _kmeans_args("kmeans", x, x.reshape(-1, x.shape[-1])[:1], metric)
+        pool = torch.nonzero(torch.isfinite(x2).all(dim=1)).reshape(-1).cpu().numpy()
+        if pool.size < k:
+            raise ValueError(f"kmeans: {pool.size} rows without NaN or infinity, fewer than k = {k}")
+        rng = np.random.default_rng(seed)
+        inits = [x2[torch.as_tensor(np.sort(rng.choice(pool, size=k, replace=False)), device=x2.device)]
+                 for _ in range(int(n_init))]
+    best = None
+    for init in inits:
+        cent, prev, n_iter = init.contiguous().clone(), None, 0
+        while True:
+            labels, dist = _assign(x2, cent, code)
+            if (prev is not None and torch.equal(labels, prev)) or n_iter >= max_iter:
+                break
+            cent, _ = _update(x2, labels, cent, code)
+            prev, n_iter = labels, n_iter + 1
+        inertia = float(torch.nansum(dist))
+        if best is None or inertia < best[2]:
+            best = (cent, labels.view(lead), inertia, n_iter)
+    return best
+
+
+def state_stats(labels, k):
+    """What a sweep is fitted on (wc_state_stats): labels [M][B] or [M] int32 device tensor, time-major,
+    k states -> a dict of "occupancy" [B][k] (the share of the labelled times spent in each state),
+    "dwell" [B][k] (the mean length in samples of the maximal runs of a state; a -1 ends a run) and
+    "trans" [B][k][k] (the transition probabilities between consecutive labelled times, self-transitions
+    included), without B for 1-D labels.  Counted in integers, divided once; NaN where there is nothing
+    to divide by.  A label outside -1 .. k - 1 counts as -1."""
+    if not isinstance(labels, torch.Tensor) or labels.dtype != torch.int32 or labels.dim() not in (1, 2):
+        raise TypeError("state_stats: labels must be a [M][B] or [M] int32 device tensor")
+    k = int(k)
+    single = labels.dim() == 1
+    M, B = labels.shape[0], (1 if single else labels.shape[1])
+    if M < 1 or B < 1 or k < 1 or k > KMEANS_MAX_K:
+        raise ValueError(f"state_stats: M = {M}, B = {B}, K = {k}: needs M >= 1, B >= 1 and 1 <= K <= {KMEANS_MAX_K}")
+    labels = labels.contiguous()
+    f64 = dict(dtype=torch.float64, device=labels.device)
+    occ, dwell, trans = torch.empty((B, k), **f64), torch.empty((B, k), **f64), torch.empty((B, k, k), **f64)
+    _lib.check(_lib.lib().wc_state_stats(B, M, k, _lib.ptr(labels), _lib.ptr(occ), _lib.ptr(dwell), _lib.ptr(trans),
+                                         _lib.stream_handle()), "wc_state_stats")
+    res = dict(occupancy=occ, dwell=dwell, trans=trans)
+    return {n: v[0] for n, v in res.items()} if single else res
+
+
+def leida_states(vec, centroids, metric="cosine"):
+    """LEiDA's third stage: vec [M][B][N] or [M][N] (leida's eigenvectors), centroids [K][N] (kmeans of
+    empirical or pooled eigenvectors) -> a dict of "labels" [M][B] int32 (kmeans_assign; -1 for a NaN
+    eigenvector) and state_stats' "occupancy" [B][K], "dwell" [B][K], "trans" [B][K][K], without B for a
+    2-D vec."""
+    x2, cent, code, lead = _kmeans_args("leida_states", vec, centroids, metric)
+    labels = _assign(x2, cent, code)[0].view(lead)
+    return dict(labels=labels, **state_stats(labels, cent.shape[0]))
+
+
+def state_kl(p, q):
+    """The symmetrised Kullback-Leibler divergence 0.5 (KL(p||q) + KL(q||p)) between occupancy rows
+    p [B][K] or [K] and an empirical one q [K] -> [B] (a scalar tensor for one row): the distance a
+    sweep is fitted on after LEiDA (Deco et al. 2019).  0 log 0 = 0; an entry that is 0 on one side only
+    gives +inf; a row with a NaN gives NaN.  Plain torch, like fcd_ks."""
+    if not isinstance(p, torch.Tensor) or p.dtype != torch.float64 or p.dim() not in (1, 2):
+        raise TypeError("state_kl: p must be a [B][K] or [K] fp64 tensor")
+    q = torch.as_tensor(np.asarray(q.cpu() if isinstance(q, torch.Tensor) else q, dtype=np.float64)).to(p.device)
+    if q.dim() != 1 or q.shape[0] != p.shape[-1] or q.numel() == 0:
+        raise ValueError(f"state_kl: q must be one row of K = {p.shape[-1]} entries")
+    q = q.expand_as(p)
+
+    def kl(a, b):
+        t = torch.where(a > 0, a * (torch.log(a) - torch.log(b)), torch.zeros_like(a))
+        return torch.where(torch.isnan(a) | torch.isnan(b), torch.full_like(a, float("nan")), t).sum(dim=-1)
+
+    return 0.5 * (kl(p, q) + kl(q, p))
+
+
 def welch_peak(E_t, fs=500.0, want_psd=False):
     """whole_sweep_both.py:90-95 for E [T][B][N] (time-major): peak frequency per
     simulation (and the node-mean PSD)."""

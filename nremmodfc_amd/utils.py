@@ -290,6 +290,55 @@ def fcd(series, window=30, step=1, method="corr", trim=0, device="cuda"):
     return sigchain.fcd(xt, window, step).cpu().numpy()
 
 
+def leida(series, dt, freqs, centroids=None, k=None, trim=0, metric="cosine", device="cuda"):
+    """LEiDA (Cabral et al. 2017) of series (time, rois) or (time, B, N) on the device: utils.envelope's
+    Bessel order-3 band-pass filtfilt over freqs (Hz, at sampling step dt; freqs=None: series is taken
+    as band-limited already), then sigchain.leida: the leading eigenvector of every instantaneous
+    phase-coherence matrix, less `trim` samples at either end.  numpy in (float32 accepted), a dict of
+    numpy arrays out: "vec" (time - 2 trim, [B,] N) and "share" (time - 2 trim[, B]).  With centroids
+    (K, N) also sigchain.leida_states' "labels", "occupancy", "dwell" and "trans"; with an integer k
+    instead, the eigenvectors of all simulations and times are clustered first (sigchain.kmeans, seed 0)
+    and "centroids", "inertia" and "n_iter" are returned too.  2 <= N <= 1024, K <= 32."""
+    x = np.asarray(series)
+    if x.dtype.kind not in "fiub":
+        raise TypeError(f"leida: series must be real numbers, not {x.dtype}")
+    if x.ndim not in (2, 3) or x.size == 0:
+        raise ValueError("series must be (time, rois) or (time, B, N)")
+    if freqs is not None and len(freqs) != 2:
+        raise ValueError("freqs must be [fmin, fmax] or None")
+    if metric not in sigchain.KMEANS_METRICS:
+        raise ValueError(f"leida: unknown metric {metric!r}, must be one of {list(sigchain.KMEANS_METRICS)}")
+    if centroids is not None and k is not None:
+        raise ValueError("leida: give centroids or k, not both")
+    if k is not None and not 1 <= int(k) <= sigchain.KMEANS_MAX_K:
+        raise ValueError(f"leida: K = {k}: needs 1 <= K <= {sigchain.KMEANS_MAX_K}")
+    N = x.shape[-1]
+    if centroids is not None:
+        centroids = np.array(centroids, dtype=np.float64, order="C")
+        if centroids.ndim != 2 or centroids.shape[1] != N or not 1 <= centroids.shape[0] <= sigchain.KMEANS_MAX_K:
+            raise ValueError(f"leida: centroids must be (K, N = {N}) with 1 <= K <= {sigchain.KMEANS_MAX_K}")
+    if N < 2 or N > sigchain.LEIDA_MAX_N or int(trim) < 0 or x.shape[0] - 2 * int(trim) < 1:
+        raise ValueError(f"leida: needs 2 <= N <= {sigchain.LEIDA_MAX_N}, trim >= 0 and time - 2 trim >= 1 "
+                         f"(N = {N}, time = {x.shape[0]}, trim = {trim})")
+    xt = torch.from_numpy(np.array(x, dtype=np.float64, order="C")).to(device)
+    if freqs is not None:
+        (bb, ba), _ = sigchain.envelope_filters(float(dt), float(freqs[0]), float(freqs[1]), None)
+        xt = sigchain.filtfilt(bb, ba, xt)
+    vec, share = sigchain.leida(xt, trim)
+    res = dict(vec=vec, share=share)
+    if k is not None:
+        cent, _, inertia, n_iter = sigchain.kmeans(vec, int(k), metric)
+        res.update(centroids=cent)
+    elif centroids is not None:
+        cent = torch.from_numpy(centroids).to(device)
+    if k is not None or centroids is not None:
+        res.update(sigchain.leida_states(vec, cent, metric))
+    res = {n: v.cpu().numpy() for n, v in res.items()}
+    if k is not None:
+        res.update(inertia=inertia, n_iter=n_iter)
+    return res
+
+
 def kuramoto(sign):
     """utils.py:34-40: (sync, meta) of the Kuramoto order parameter of sign (T x N)
     from the phases of its analytic signal (hilbert along axis 0).
