@@ -523,6 +523,38 @@ int wc_graph_local_efficiency(int B, int N, const double* w, double* eloc, void*
 int wc_graph_clustering(int B, int N, const double* w, double* clustering, double* transitivity,
                         double* strengths, int* degrees, void* stream);
 
+/* Node measures of the same batch (wc_graph.hip): which nodes are hubs, and of what kind.  The
+ * argument checks are those of the three entry points above, before any device work.
+ *
+ * wc_graph_betweenness: betweenness_wei (graph_utils.py:1983-2052) of every matrix, Brandes'
+ *   algorithm with one wave per source.  w holds weights (lengths == 0: L = 1/w where w != 0) or the
+ *   lengths themselves (lengths != 0, what betweenness_wei takes); a zero is no edge and the diagonal
+ *   is ignored.  bc [B][N].  Ordered pairs are counted, so an undirected graph has twice the textbook
+ *   value, as in the reference.  A candidate path length is the single fp64 sum D[v] + L[v][w]; a
+ *   shorter one replaces the predecessors and the number of paths, an equal one adds to them; all
+ *   unsettled nodes at the minimum distance are settled together: ties resolve as in the reference.
+ *   With unique shortest paths every value is an integer and exact.  betweenness_bin (:1929-1980) is
+ *   the same on the lengths (w != 0), to rounding.  A matrix with a negative or NaN entry gets NaN in
+ *   its row of bc; the others are not affected.  No atomics: a matrix gives the same bits alone as
+ *   inside a batch.
+ *
+ * wc_graph_modules: measures of a given partition ci [B][N] int32, labels in [0, K), 1 <= K <= N; ci
+ *   4-byte aligned and overlapping no output.  Each of part, z, q may be NULL (not all three).
+ *     part [B][N]  participation_coef (:271-307): 1 - sum_m (sum_{j in m} W_ij)^2 / (sum_j W_ij)^2,
+ *                  exactly 0 where the strength is 0; degree 0: rows (undirected, out), 1: the
+ *                  transpose (in)
+ *     z    [B][N]  module_degree_zscore (:2103-2140): (k_i - mean) / std of the within-module degrees
+ *                  k_i = sum_{j in m(i)} A_ij over the node's own module, population std; A = W
+ *                  (zflag 0, 1), W^T (2), W + W^T (3).  A NaN quotient (0/0: a single-member module,
+ *                  equal degrees) is 0, as in the reference, which therefore also hides a NaN of w
+ *     q    [B]     (1/s) sum_ij (W_ij - gamma k_i^out k_j^in / s) delta(ci_i, ci_j), s = sum W: the
+ *                  modularity of the partition (Newman; Leicht & Newman for a directed matrix)
+ *   Negative weights are legal: they are summed.  A matrix with a label outside [0, K) gets NaN in
+ *   part, z and q, and nothing is indexed by that label; the others are not affected. */
+int wc_graph_betweenness(int B, int N, const double* w, int lengths, double* bc, void* stream);
+int wc_graph_modules(int B, int N, int K, const double* w, const int32_t* ci, int degree, int zflag,
+                     double gamma, double* part, double* z, double* q, void* stream);
+
 /* Dynamic functional connectivity (wc_fcd.hip): sliding-window FC with its FCD matrix (Hansen et al.
  * 2015) and the phase-coherence FCD (Deco & Kringelbach 2016).  The reference computes neither; these
  * definitions are the contract (tests/fcd_reference.py restates them in numpy).

@@ -8,6 +8,9 @@
 //   efficiency_wei(local=True) (:667-685)                  -> wc_graph_local_efficiency
 //   clustering_coef_wu (:1305-1323), transitivity_wu (:1673-1689), strengths_und (:1766-1778),
 //   degrees_und (:1721-1737)                               -> wc_graph_clustering
+//   betweenness_wei (:1983-2052), betweenness_bin (:1929-1980) -> wc_graph_betweenness
+//   participation_coef (:271-307), module_degree_zscore (:2103-2140), and the modularity Q of a
+//   given partition                                        -> wc_graph_modules
 // No symmetry is assumed: the expressions are evaluated as the reference writes them, so a directed
 // matrix gives what the reference gives.
 //
@@ -359,7 +362,328 @@ size_t clustering_lds_bytes(int N) {
     return sizeof(double) * (Np * Np + Np) + sizeof(int) * (size_t)N;
 }
 
-// ---- argument checks shared by the three entry points ----
+// The node measures below repeat the reference's sums and products one rounding at a time.
+#pragma clang fp contract(off)
+
+// ---- wc_graph_betweenness: one workgroup per matrix, one wave per source ----
+// Brandes' algorithm as betweenness_wei writes it (graph_utils.py:1983-2052).  The lengths lie in LDS;
+// wave k of the 16 takes the sources k, k + 16, ...; lane l owns the nodes l and l + 64 and keeps, of
+// each, the distance D, the number of shortest paths NP, the dependency DP, the round in which it was
+// settled and its predecessors as a 96-bit mask, all in registers.  One Dijkstra round: the wave-wide minimum
+// of D over the unsettled nodes, a ballot of the nodes at that minimum (all of them are settled
+// together), and for every settled v one conflict-free row read L[v][.] with the relaxation
+// D[v] + L[v][w] in every lane: < replaces predecessors and path count, == adds to them.  The
+// dependency pass walks the rounds backwards (a predecessor is settled in an earlier round than its
+// successor, so a round's DP is final when it is reached), a round's nodes in descending order like
+// the reference's Q: (1 + DP[w]) / NP[w] and w's mask are broadcast and the lanes whose bit is set add
+// that times their NP.  NP[w] == 1 for a whole round (always, where shortest paths are unique) skips
+// the division: x / 1 is x.  BC adds up per lane over the wave's sources; the waves combine
+// through LDS in a fixed order.  No atomics: the bits do not depend on the batch.
+template <int CTRL, int ROWS>
+__device__ __forceinline__ uint32_t min_dpp(uint32_t x) {  // a lane that the move leaves out keeps its own
+    const uint32_t y = (uint32_t)__builtin_amdgcn_update_dpp((int)x, (int)x, CTRL, ROWS, 0xf, false);
+    return y < x ? y : x;
+}
+
+// minimum of an unsigned word over the 64 lanes: within a row of 16 by quad permutes and mirrors, then
+// lane 15 of rows 0 and 2 into rows 1 and 3, lane 31 into rows 2 and 3; lane 63 holds it
+__device__ __forceinline__ uint32_t wave_min(uint32_t x) {
+    x = min_dpp<0xB1, 0xf>(x);   // quad_perm [1, 0, 3, 2]
+    x = min_dpp<0x4E, 0xf>(x);   // quad_perm [2, 3, 0, 1]
+    x = min_dpp<0x141, 0xf>(x);  // row_half_mirror
+    x = min_dpp<0x140, 0xf>(x);  // row_mirror
+    x = min_dpp<0x142, 0xa>(x);  // row_bcast:15
+    x = min_dpp<0x143, 0xc>(x);  // row_bcast:31
+    return (uint32_t)__builtin_amdgcn_readlane((int)x, 63);
+}
+
+// lane: the same in every lane of the wave
+__device__ __forceinline__ double read_lane(double x, int lane) {
+    const int lo = __builtin_amdgcn_readlane(__double2loint(x), lane);
+    const int hi = __builtin_amdgcn_readlane(__double2hiint(x), lane);
+    return __hiloint2double(hi, lo);
+}
+
+__device__ __forceinline__ uint64_t read_lane(uint64_t x, int lane) {
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)x, lane);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(x >> 32), lane);
+    return ((uint64_t)hi << 32) | lo;
+}
+
+// minimum of non-negative doubles over the 64 lanes, wave-uniform: they order as their bit patterns do,
+// so the high words first and then the low words of the lanes that hold the least high word
+__device__ __forceinline__ double wave_min(double x) {
+    const uint32_t hi = (uint32_t)__double2hiint(x), lo = (uint32_t)__double2loint(x);
+    const uint32_t mh = wave_min(hi);
+    const uint32_t ml = wave_min(hi == mh ? lo : 0xFFFFFFFFu);
+    return __hiloint2double((int)mh, (int)ml);
+}
+
+constexpr int kUnsettled = -1, kNoNode = -2;
+
+struct Node {  // one of a lane's two nodes
+    double d, np, dp;
+    int round;
+    uint64_t plo;  // predecessors 0 .. 63
+    uint32_t phi;  // predecessors 64 .. 95
+};
+
+__device__ __forceinline__ void relax(Node& x, double len, double dv, double npv, uint64_t blo, uint32_t bhi) {
+    if (x.round != kUnsettled || len == 0.0) return;
+    const double cand = dv + len;
+    if (cand < x.d) {
+        x.d = cand;
+        x.np = npv;
+        x.plo = blo;
+        x.phi = bhi;
+    } else if (cand == x.d) {
+        x.np += npv;
+        x.plo |= blo;
+        x.phi |= bhi;
+    }
+}
+
+// 16 waves a matrix: a wave's round is one chain of dependent instructions (minimum, ballot, row read,
+// relaxation), so the kernel runs at the rate at which a SIMD finds another wave to issue from.  With
+// two workgroups a CU (the lengths of 90 nodes take 65 KB of LDS) that is 8 waves a SIMD, the most
+// there are; 20,000 matrices of 90 nodes took 130, 63, 41 and 35 ms at 2, 4, 8 and 16 waves.
+constexpr int kBcThreads = 1024;
+
+__global__ void __launch_bounds__(kBcThreads) betweenness_kernel(int N, const double* __restrict__ w_all, int lengths,
+                                                                 double* __restrict__ bc) {
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    double* Ls = lds;           // [N][N] lengths, 0 where there is no edge
+    double* part = lds;         // [waves][N] the waves' sums, over the lengths once every wave is done
+    const int tid = threadIdx.x;
+    const size_t b = blockIdx.x;
+    const double* W = w_all + b * N * N;
+
+    int bad = 0;
+    for (int idx = tid; idx < N * N; idx += kBcThreads) {
+        const double x = W[idx];
+        bad |= !(x >= 0.0);  // negative or NaN
+        Ls[idx] = idx / N == idx % N ? 0.0 : (lengths ? x : length_of(x));
+    }
+    bad = __syncthreads_or(bad);
+    if (bad) {  // uniform
+        for (int i = tid; i < N; i += kBcThreads) bc[b * N + i] = NAN;
+        return;
+    }
+    const int wave = tid >> 6, lane = tid & 63;
+    const bool ok0 = lane < N, ok1 = lane + 64 < N;
+    double bc0 = 0.0, bc1 = 0.0;
+    for (int u = wave; u < N; u += kBcThreads / 64) {
+        Node a = {INFINITY, 0.0, 0.0, ok0 ? kUnsettled : kNoNode, 0, 0};  // node lane
+        Node c = {INFINITY, 0.0, 0.0, ok1 ? kUnsettled : kNoNode, 0, 0};  // node lane + 64
+        if (lane == (u & 63)) {
+            Node& src = u < 64 ? a : c;
+            src.d = 0.0;
+            src.np = 1.0;
+        }
+        int rounds = 0;
+        while (rounds < N) {  // every round settles a node or more
+            double m = fmin(a.round == kUnsettled ? a.d : INFINITY, c.round == kUnsettled ? c.d : INFINITY);
+            m = wave_min(m);
+            if (!(m < INFINITY)) break;  // every node settled, or the rest out of reach
+            const bool s0 = a.round == kUnsettled && a.d == m, s1 = c.round == kUnsettled && c.d == m;
+            uint64_t v0 = __ballot(s0);
+            uint32_t v1 = (uint32_t)__ballot(s1);
+            if (s0) a.round = rounds;
+            if (s1) c.round = rounds;
+            while (v0) {  // ascending, as the reference goes through V
+                const int v = __builtin_amdgcn_readfirstlane(__ffsll((unsigned long long)v0) - 1);
+                v0 &= v0 - 1;
+                const double npv = read_lane(a.np, v);
+                const double* row = Ls + v * N;
+                relax(a, ok0 ? row[lane] : 0.0, m, npv, 1ull << v, 0u);
+                relax(c, ok1 ? row[lane + 64] : 0.0, m, npv, 1ull << v, 0u);
+            }
+            while (v1) {
+                const int l = __builtin_amdgcn_readfirstlane(__ffs(v1) - 1);
+                v1 &= v1 - 1;
+                const double npv = read_lane(c.np, l);
+                const double* row = Ls + (l + 64) * N;
+                relax(a, ok0 ? row[lane] : 0.0, m, npv, 0ull, 1u << l);
+                relax(c, ok1 ? row[lane + 64] : 0.0, m, npv, 0ull, 1u << l);
+            }
+            ++rounds;
+        }
+        // dependencies: the nodes out of reach first (they count only where an infinite length made
+        // them somebody's successor), then the rounds backwards; round 0 is the source alone
+        for (int r = rounds; r >= 1; --r) {
+            const bool last = r == rounds;
+            const bool m0 = last ? (a.round == kUnsettled && (a.plo | a.phi)) : a.round == r;
+            const bool m1 = last ? (c.round == kUnsettled && (c.plo | c.phi)) : c.round == r;
+            if (m0) bc0 += a.dp;
+            if (m1) bc1 += c.dp;
+            double c0 = 1.0 + a.dp, c1 = 1.0 + c.dp;
+            if (__any((m0 && a.np != 1.0) || (m1 && c.np != 1.0))) {
+                c0 /= a.np;
+                c1 /= c.np;
+            }
+            uint32_t w1 = (uint32_t)__ballot(m1);
+            uint64_t w0 = __ballot(m0);
+            while (w1) {
+                const int l = __builtin_amdgcn_readfirstlane(31 - __clz((int)w1));
+                w1 &= ~(1u << l);
+                const double coef = read_lane(c1, l);
+                const uint64_t plo = read_lane(c.plo, l);
+                const uint64_t phi = (uint32_t)__builtin_amdgcn_readlane((int)c.phi, l);
+                if ((plo >> lane) & 1) a.dp += coef * a.np;
+                if ((phi >> lane) & 1) c.dp += coef * c.np;
+            }
+            while (w0) {
+                const int l = __builtin_amdgcn_readfirstlane(63 - __clzll((long long)w0));
+                w0 &= ~(1ull << l);
+                const double coef = read_lane(c0, l);
+                const uint64_t plo = read_lane(a.plo, l);
+                const uint64_t phi = (uint32_t)__builtin_amdgcn_readlane((int)a.phi, l);
+                if ((plo >> lane) & 1) a.dp += coef * a.np;
+                if ((phi >> lane) & 1) c.dp += coef * c.np;
+            }
+        }
+    }
+    __syncthreads();
+    if (ok0) part[wave * N + lane] = bc0;
+    if (ok1) part[wave * N + lane + 64] = bc1;
+    __syncthreads();
+    if (tid < N) {
+        double s = part[tid];
+        for (int k = 1; k < kBcThreads / 64; ++k) s += part[k * N + tid];
+        bc[b * N + tid] = s;
+    }
+}
+
+size_t betweenness_lds_bytes(int N) { return sizeof(double) * (size_t)N * (N > kBcThreads / 64 ? N : kBcThreads / 64); }
+
+// ---- wc_graph_modules: one workgroup per matrix, thread i for node i ----
+// The matrix lies in LDS with an odd row stride (a thread walks its row or its column without bank
+// conflicts); perm lists the nodes module by module, ascending within a module, so that a thread
+// meets every module's members together and needs no table of per-module sums.  Sums run in index
+// order within a module and over the modules in ascending order, as the reference's loops do.
+__global__ void __launch_bounds__(kThreads) modules_kernel(int N, int K, const double* __restrict__ w_all,
+                                                           const int32_t* __restrict__ ci_all, int degree, int zflag,
+                                                           double gamma, double* __restrict__ part,
+                                                           double* __restrict__ z, double* __restrict__ q) {
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    const int Ns = N | 1;
+    double* Ws = lds;                                // [N][Ns]
+    double* kout = Ws + N * Ns;                      // [N] row sums
+    double* kin = kout + N;                          // [N] column sums
+    double* koi = kin + N;                           // [N] within-module degrees
+    double* qrow = koi + N;                          // [N] a row's share of Q
+    int* lab = reinterpret_cast<int*>(qrow + N);     // [N] labels
+    int* perm = lab + N;                             // [N] nodes by module
+    const int tid = threadIdx.x;
+    const size_t b = blockIdx.x;
+    const double* W = w_all + b * N * N;
+
+    for (int idx = tid; idx < N * N; idx += kThreads) Ws[idx / N * Ns + idx % N] = W[idx];
+    int bad = 0;
+    if (tid < N) {
+        const int c = ci_all[b * N + tid];
+        bad = c < 0 || c >= K;
+        lab[tid] = c;
+    }
+    bad = __syncthreads_or(bad);
+    if (bad) {  // uniform: a label out of range; nothing is indexed by it
+        for (int i = tid; i < N; i += kThreads) {
+            if (part) part[b * N + i] = NAN;
+            if (z) z[b * N + i] = NAN;
+        }
+        if (q && tid == 0) q[b] = NAN;
+        return;
+    }
+    const int i = tid < N ? tid : 0;
+    const int mine = lab[i];
+    int first = 0, count = 0;  // of this node's module in perm
+    {
+        int before = 0;
+        for (int j = 0; j < N; ++j) {
+            const int c = lab[j];
+            first += c < mine;
+            count += c == mine;
+            before += c == mine && j < i;
+        }
+        if (tid < N) perm[first + before] = i;
+    }
+    __syncthreads();
+
+    if (part && tid < N) {  // participation_coef (graph_utils.py:271-307)
+        const int si = degree ? 1 : Ns, sj = degree ? Ns : 1;  // degree 'in': the transpose
+        double ko = 0.0, kc2 = 0.0, km = 0.0;
+        for (int j = 0; j < N; ++j) ko += Ws[i * si + j * sj];
+        int cur = lab[perm[0]];
+        for (int p = 0; p < N; ++p) {
+            const int j = perm[p];
+            if (lab[j] != cur) {
+                kc2 += km * km;
+                km = 0.0;
+                cur = lab[j];
+            }
+            km += Ws[i * si + j * sj];
+        }
+        kc2 += km * km;
+        part[b * N + i] = ko == 0.0 ? 0.0 : 1.0 - kc2 / (ko * ko);
+    }
+    if (z) {  // module_degree_zscore (graph_utils.py:2103-2140)
+        if (tid < N) {
+            double k = 0.0;
+            for (int p = first; p < first + count; ++p) {
+                const int j = perm[p];
+                const double out = Ws[i * Ns + j], in = Ws[j * Ns + i];
+                k += zflag == 3 ? out + in : (zflag == 2 ? in : out);
+            }
+            koi[i] = k;
+        }
+        __syncthreads();
+        if (tid < N) {
+            double s = 0.0, v = 0.0;
+            for (int p = first; p < first + count; ++p) s += koi[perm[p]];
+            const double mean = s / count;
+            for (int p = first; p < first + count; ++p) {
+                const double d = fabs(koi[perm[p]] - mean);
+                v += d * d;
+            }
+            const double zz = (koi[i] - mean) / sqrt(v / count);  // the population's deviation
+            z[b * N + i] = isnan(zz) ? 0.0 : zz;                  // the reference's Z[isnan(Z)] = 0
+        }
+    }
+    if (q) {  // Newman / Leicht-Newman modularity of the partition
+        if (tid < N) {
+            double ro = 0.0, co = 0.0;
+            for (int j = 0; j < N; ++j) {
+                ro += Ws[i * Ns + j];
+                co += Ws[j * Ns + i];
+            }
+            kout[i] = ro;
+            kin[i] = co;
+        }
+        __syncthreads();
+        double s = 0.0;
+        for (int j = 0; j < N; ++j) s += kout[j];
+        if (tid < N) {
+            double acc = 0.0;
+            for (int p = first; p < first + count; ++p) {
+                const int j = perm[p];
+                acc += Ws[i * Ns + j] - gamma * kout[i] * kin[j] / s;
+            }
+            qrow[i] = acc;
+        }
+        __syncthreads();
+        if (tid == 0) {
+            double acc = 0.0;
+            for (int j = 0; j < N; ++j) acc += qrow[j];
+            q[b] = acc / s;
+        }
+    }
+}
+
+size_t modules_lds_bytes(int N) {
+    return sizeof(double) * ((size_t)N * (N | 1) + 4 * (size_t)N) + sizeof(int) * 2 * (size_t)N;
+}
+
+// ---- argument checks shared by the entry points ----
 struct Out {
     const void* p;
     size_t bytes;  // of the whole output
@@ -440,6 +764,41 @@ int wc_graph_clustering(int B, int N, const double* w, double* clustering, doubl
     hipLaunchKernelGGL(clustering_kernel, dim3(B), dim3(kThreads), lds, static_cast<hipStream_t>(stream), N, w,
                        clustering, transitivity, strengths, degrees);
     return wc_hip_check("wc_graph_clustering");
+}
+
+int wc_graph_betweenness(int B, int N, const double* w, int lengths, double* bc, void* stream) {
+    wc_clear_err();
+    const size_t b = B > 0 ? (size_t)B : 0, n = N > 0 ? (size_t)N : 0;
+    const Out outs[1] = {{bc, b * n * 8}};
+    if (int rc = check_args("wc_graph_betweenness", B, N, w, outs, 1, false)) return rc;
+    const size_t lds = betweenness_lds_bytes(N);
+    if (int rc = raise_lds(betweenness_kernel, lds)) return rc;
+    hipLaunchKernelGGL(betweenness_kernel, dim3(B), dim3(kBcThreads), lds, static_cast<hipStream_t>(stream), N, w,
+                       lengths, bc);
+    return wc_hip_check("wc_graph_betweenness");
+}
+
+int wc_graph_modules(int B, int N, int K, const double* w, const int32_t* ci, int degree, int zflag, double gamma,
+                     double* part, double* z, double* q, void* stream) {
+    wc_clear_err();
+    const size_t b = B > 0 ? (size_t)B : 0, n = N > 0 ? (size_t)N : 0;
+    const Out outs[3] = {{part, b * n * 8}, {z, b * n * 8}, {q, b * 8}};
+    if (int rc = check_args("wc_graph_modules", B, N, w, outs, 3, false)) return rc;
+    if (K < 1 || K > N) return wc_set_err(WC_EINVAL, "wc_graph_modules: K must be in [1, N]");
+    if (!ci) return wc_set_err(WC_EINVAL, "wc_graph_modules: ci is NULL");
+    if ((uintptr_t)ci & 3) return wc_set_err(WC_EINVAL, "wc_graph_modules: ci must be 4-byte aligned");
+    if (degree != 0 && degree != 1) return wc_set_err(WC_EINVAL, "wc_graph_modules: degree must be 0 (out) or 1 (in)");
+    if (zflag < 0 || zflag > 3) return wc_set_err(WC_EINVAL, "wc_graph_modules: zflag must be 0, 1, 2 or 3");
+    const uintptr_t c0 = (uintptr_t)ci, c1 = c0 + b * n * sizeof(int32_t);
+    for (const Out& o : outs) {
+        const uintptr_t p0 = (uintptr_t)o.p, p1 = p0 + o.bytes;
+        if (o.p && p0 < c1 && c0 < p1) return wc_set_err(WC_EINVAL, "wc_graph_modules: an output must not alias ci");
+    }
+    const size_t lds = modules_lds_bytes(N);
+    if (int rc = raise_lds(modules_kernel, lds)) return rc;
+    hipLaunchKernelGGL(modules_kernel, dim3(B), dim3(kThreads), lds, static_cast<hipStream_t>(stream), N, K, w, ci,
+                       degree, zflag, gamma, part, z, q);
+    return wc_hip_check("wc_graph_modules");
 }
 
 }  // extern "C"

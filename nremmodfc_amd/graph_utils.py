@@ -6,9 +6,13 @@ reference's, host numpy on N x N matrices, O(N^2) bookkeeping once per optimiser
 iteration.  distance_wei, efficiency_wei, clustering_coef_wu, transitivity_wu,
 strengths_und and degrees_und (with cuberoot, invert and the host charpath) run
 on the device through sigchain.graph_measures, for one matrix or a [B, N, N]
-stack; torch and the library are imported on first use, so importing this module
-stays light.  The rest of the 2,600-line toolbox (modularity, betweenness, rich
-club, signed and directed variants) is analysis outside the sweep path.
+stack; betweenness_wei and betweenness_bin through sigchain.graph_betweenness,
+participation_coef and module_degree_zscore through
+sigchain.graph_module_measures (which also gives the modularity Q of a given
+partition).  torch and the library are imported on first use, so importing this
+module stays light.  The rest of the 2,600-line toolbox (partition search by
+Louvain, Newman and consensus, rich club, assortativity, signed and null-model
+variants) is analysis outside the sweep path.
 """
 import numpy as np
 
@@ -154,3 +158,67 @@ def strengths_und(CIJ):
 def degrees_und(CIJ):
     """Node degrees: non-zeros of every column (graph_utils.py:1721-1737)."""
     return _device(_matrices("degrees_und", CIJ, False), ("degrees",))[0].astype(np.float64)
+
+
+# ---- node measures on the device (sigchain.graph_betweenness, sigchain.graph_module_measures) ----
+
+def _betweenness(a):
+    import torch
+
+    from . import sigchain
+    return sigchain.graph_betweenness(torch.from_numpy(a).cuda(), lengths=True).cpu().numpy()
+
+
+def betweenness_wei(G):
+    """Node betweenness centrality over the connection lengths G (graph_utils.py:1983-2052): ordered
+    pairs, so an undirected graph has twice the textbook value."""
+    return _betweenness(_matrices("betweenness_wei", G, True))
+
+
+def betweenness_bin(G):
+    """Node betweenness centrality of a binary graph (graph_utils.py:1929-1980): the same kernel on
+    the lengths (G != 0)."""
+    return _betweenness((_matrices("betweenness_bin", G, False) != 0).astype(np.float64))
+
+
+def _labels(name, ci, a):
+    """ci [N] or, with a stack, [B, N] -> (int32 labels 0 .. K-1 through np.unique, as the reference
+    relabels them, K)."""
+    ci = np.asarray(ci)
+    N = a.shape[-1]
+    if ci.ndim not in (1, 2) or ci.shape[-1] != N or (ci.ndim == 2 and (a.ndim != 3 or ci.shape[0] != a.shape[0])):
+        raise ValueError(f"{name}: ci needs one label per node, [N] or [B, N] with a stack, got shape {ci.shape} "
+                         f"for matrices of shape {a.shape}")
+    rows = [np.unique(row, return_inverse=True)[1].reshape(-1) for row in ci.reshape(-1, N)]
+    lab = np.ascontiguousarray(np.array(rows, dtype=np.int32).reshape(ci.shape))
+    return lab, int(lab.max()) + 1
+
+
+def _modules(a, lab, K, name, **kw):
+    import torch
+
+    from . import sigchain
+    got = sigchain.graph_module_measures(torch.from_numpy(a).cuda(), torch.from_numpy(lab).cuda(), (name,),
+                                         n_modules=K, **kw)
+    return got[name].cpu().numpy()
+
+
+def participation_coef(W, ci, degree="undirected"):
+    """Participation coefficient of every node for the partition ci (graph_utils.py:271-307); degree
+    'undirected', 'out' (rows) or 'in' (columns)."""
+    a = _matrices("participation_coef", W, False)
+    if degree not in ("undirected", "in", "out"):
+        raise ValueError(f"participation_coef: degree {degree!r}, must be 'undirected', 'in' or 'out'")
+    lab, K = _labels("participation_coef", ci, a)
+    return _modules(a, lab, K, "participation", degree=degree)
+
+
+def module_degree_zscore(W, ci, flag=0):
+    """Within-module degree z-score of every node for the partition ci (graph_utils.py:2103-2140);
+    flag 0 undirected, 1 in, 2 out, 3 in and out, as the reference evaluates them: W, W, W^T,
+    W + W^T."""
+    a = _matrices("module_degree_zscore", W, False)
+    if isinstance(flag, bool) or flag not in (0, 1, 2, 3):
+        raise ValueError(f"module_degree_zscore: flag {flag!r}, must be 0, 1, 2 or 3")
+    lab, K = _labels("module_degree_zscore", ci, a)
+    return _modules(a, lab, K, "zscore", zflag=int(flag))

@@ -400,7 +400,93 @@ def graph_measures(w, measures=GRAPH_MEASURES, lengths=False, include_infinite=T
     return {m: (res[m][0] if single else res[m]) for m in names}
 
 
-FCD_MAX_N = 96            # wc_fcd, wc_fcd_phase: one window's correlation matrix, a tile's phasors per workgroup
+def _graph_stack(name, w):
+    """(w contiguous, single, B, N) of a [B][N][N] or [N][N] fp64 tensor, refused before the device is touched."""
+    if not isinstance(w, torch.Tensor) or w.dtype != torch.float64 or w.dim() not in (2, 3) \
+            or w.shape[-1] != w.shape[-2]:
+        raise TypeError(f"{name}: w must be a [B][N][N] or [N][N] fp64 device tensor")
+    single = w.dim() == 2
+    B, N = (1 if single else w.shape[0]), w.shape[-1]
+    if N < 2 or N > GRAPH_MAX_N or B < 1:
+        raise ValueError(f"{name}: N = {N}, B = {B}: needs B >= 1 and 2 <= N <= {GRAPH_MAX_N} "
+                         "(one matrix per workgroup, in LDS)")
+    return w.contiguous(), single, B, N
+
+
+def graph_betweenness(w, lengths=False):
+    """Node betweenness centrality of B matrices on the device (wc_graph_betweenness; the reference's
+    betweenness_wei): w [B][N][N] or [N][N] fp64 device tensor, 2 <= N <= 96 -> [B][N], or [N] for a
+    single matrix.  w holds weights, with the connection lengths 1/w where w != 0, or, with
+    lengths=True, the lengths themselves; a zero is no edge, the diagonal is ignored, no symmetry is
+    assumed.  Ordered pairs are counted: an undirected graph has twice the textbook value, as in the
+    reference; divide by (N - 1)(N - 2) for the range [0, 1].  Ties between shortest paths resolve as
+    in the reference; with unique shortest paths every value is an exact integer.  A matrix with a
+    negative or NaN entry has NaN in its row.  The same matrix gives the same bits in any batch.
+
+    Composes with fc_metrics(..., want_fc=True) and hma, like graph_measures."""
+    w, single, B, N = _graph_stack("graph_betweenness", w)
+    bc = torch.empty((B, N), dtype=torch.float64, device=w.device)
+    _lib.check(_lib.lib().wc_graph_betweenness(B, N, _lib.ptr(w), int(bool(lengths)), _lib.ptr(bc),
+                                               _lib.stream_handle()), "wc_graph_betweenness")
+    return bc[0] if single else bc
+
+
+GRAPH_MODULE_MEASURES = ("participation", "zscore", "modularity")
+GRAPH_MODULE_DEGREES = {"undirected": 0, "out": 0, "in": 1}
+
+
+def graph_module_measures(w, ci, measures=GRAPH_MODULE_MEASURES, degree="undirected", zflag=0, gamma=1.0,
+                          n_modules=None):
+    """Measures of a given partition of B matrices on the device (wc_graph_modules): w [B][N][N] or
+    [N][N] fp64 device tensor, 2 <= N <= 96; ci int32 device tensor of module labels, [B][N] or [N]
+    shared by every matrix, labels in [0, n_modules) (n_modules=None: [0, N)) -> a dict from measure
+    name to a device tensor.
+
+    "participation" [N]: the participation coefficient (the reference's participation_coef),
+    1 - sum_m (sum_{j in m} W_ij)^2 / (sum_j W_ij)^2, 0 where the strength is 0; degree "undirected" or
+    "out" uses rows, "in" the transpose.  "zscore" [N]: the within-module degree z-score
+    (module_degree_zscore) with the reference's flag as zflag: 0 undirected, 1 W, 2 W^T, 3 W + W^T;
+    population standard deviation; where the reference's NaN rule gives 0 (a single-member module, a
+    module of equal degrees) this gives 0, and like the reference it therefore cannot tell a NaN in w
+    from such a case: a NaN entry shows as 0 in the z-scores of its module.  "modularity": Q =
+    (1/s) sum_ij (W_ij - gamma k_i^out k_j^in / s) delta(ci_i, ci_j), s = sum W (Newman; Leicht &
+    Newman for a directed matrix).  Negative weights are summed as they are.  Only the outputs asked
+    for are allocated.  A matrix with a label out of range has NaN in every measure; no label is read
+    back to the host."""
+    names = (measures,) if isinstance(measures, str) else tuple(measures)
+    for m in names:
+        if m not in GRAPH_MODULE_MEASURES:
+            raise ValueError(f"graph_module_measures: unknown measure {m!r}, must be one of "
+                             f"{list(GRAPH_MODULE_MEASURES)}")
+    if not names:
+        raise ValueError(f"graph_module_measures: no measure asked for, choose from {list(GRAPH_MODULE_MEASURES)}")
+    names = tuple(dict.fromkeys(names))
+    if degree not in GRAPH_MODULE_DEGREES:
+        raise ValueError(f"graph_module_measures: degree {degree!r}, must be one of {list(GRAPH_MODULE_DEGREES)}")
+    if isinstance(zflag, bool) or not isinstance(zflag, int) or not 0 <= zflag <= 3:
+        raise ValueError(f"graph_module_measures: zflag {zflag!r}, must be 0, 1, 2 or 3")
+    w, single, B, N = _graph_stack("graph_module_measures", w)
+    if not isinstance(ci, torch.Tensor) or ci.dtype != torch.int32 or ci.dim() not in (1, 2) \
+            or ci.shape[-1] != N or (ci.dim() == 2 and ci.shape[0] != B):
+        raise TypeError(f"graph_module_measures: ci must be an int32 device tensor [N] or [B][N] with N = {N}, B = {B}")
+    K = N if n_modules is None else int(n_modules)
+    if K < 1 or K > N:
+        raise ValueError(f"graph_module_measures: n_modules = {n_modules}, must be in [1, N = {N}]")
+    if ci.device != w.device:
+        raise ValueError("graph_module_measures: ci and w must be on the same device")
+    ci = (ci.expand(B, N) if ci.dim() == 1 else ci).contiguous()
+
+    def new(m, *shape):
+        return torch.empty((B,) + shape, dtype=torch.float64, device=w.device) if m in names else None
+
+    res = {"participation": new("participation", N), "zscore": new("zscore", N), "modularity": new("modularity")}
+    _lib.check(_lib.lib().wc_graph_modules(B, N, K, _lib.ptr(w), _lib.ptr(ci), GRAPH_MODULE_DEGREES[degree], zflag,
+                                           float(gamma), _lib.ptr(res["participation"]), _lib.ptr(res["zscore"]),
+                                           _lib.ptr(res["modularity"]), _lib.stream_handle()), "wc_graph_modules")
+    return {m: (res[m][0] if single else res[m]) for m in names}
+
+
+FCD_MAX_N = 96           # wc_fcd, wc_fcd_phase: one window's correlation matrix, a tile's phasors per workgroup
 FCD_MAX_WINDOWS = 4096    # WC_FCD_MAX_WINDOWS
 FCD_PHASE_MAX_M = 4096    # WC_FCD_PHASE_MAX_M
 FCD_WS_CAP = 1 << 30      # wc_fcd: workspace ceiling (chunks of simulations beyond it)
