@@ -555,6 +555,42 @@ int wc_graph_betweenness(int B, int N, const double* w, int lengths, double* bc,
 int wc_graph_modules(int B, int N, int K, const double* w, const int32_t* ci, int degree, int zflag,
                      double gamma, double* part, double* z, double* q, void* stream);
 
+/* Partition search on the same batch (wc_louvain.hip): the ci that wc_graph_modules takes.  Every
+ * argument is checked before any device work: B, R >= 1, 2 <= N <= 96 (more: WC_EUNSUPPORTED),
+ * B R < 2^31; fp64 and uint64 arrays 8-byte, int32 arrays 4-byte aligned; no output overlapping an
+ * input or another output.
+ *
+ * wc_graph_louvain: community_louvain (graph_utils.py:958-1122) from the objective matrix on, for
+ *   every pair of a matrix and a seed.  obj [B][N][N] is the reference's B after :1032-1052 (the
+ *   modularity matrix W - gamma k_out k_in^T / s, the Potts matrix, or any other), norm [B] its s;
+ *   ci0 NULL (every node its own module) or [B][N] int32 starting labels in [0, N), relabelled as
+ *   np.unique does; seeds [R] uint64.
+ *     ci   [B][R][N]  int32, labels 0 .. K-1: the reference's final labelling minus 1
+ *     q    [B][R]     the objective of that partition, trace of the pooled matrix / s
+ *     info [B][R][2]  int32, levels (passes of the outer loop) and node sweeps in all; may be NULL
+ *   Per level, sweeps over the current nodes until none moves; node u of module ma has
+ *   dQ = Hnm[u,:] - Hnm[u,ma] + obj[u,u], dQ[ma] = 0, and moves where max dQ > 1e-10 to the lowest
+ *   index that attains the maximum (np.argmax), an empty module included.  Between levels the
+ *   modules are relabelled as np.unique does and obj is pooled over module pairs, the upper triangle
+ *   computed and mirrored; levels go on while q - q0 > 1e-10.  No symmetry is assumed.
+ *   The visiting order is the engine's own, as numpy's permutation cannot be drawn here: sweeps
+ *   are numbered t = 0, 1, 2, ... over all levels of a run, and sweep t visits n nodes in the stable
+ *   argsort of n 32-bit keys, key i = word i % 4 of the Philox block above with step = t,
+ *   quad = i / 4, simkey = seed; ties go to the lower index.  It depends on seed and t only.
+ *   A matrix whose obj or norm holds NaN or inf, or whose ci0 holds a label outside [0, N), gets
+ *   ci = -1, q = NaN and info = 0 in all its runs; a run whose level has not settled after 1000
+ *   sweeps (the reference raises) gets ci = -1 and q = NaN; nothing else is affected.  Fixed
+ *   summation order and no atomics: a (matrix, seed) pair gives the same bits alone as in any batch.
+ *
+ * wc_graph_agreement: agreement (:890-932).  ci [B][R][N] int32, R partitions of every matrix.
+ *     D [B][N][N]  the number of the R partitions in which i and j share a label, exact; 0 on the
+ *                  diagonal
+ *   A negative label anywhere in a matrix's partitions (a run that wc_graph_louvain refused) makes
+ *   its D NaN; the others are not affected. */
+int wc_graph_louvain(int B, int R, int N, const double* obj, const double* norm, const int32_t* ci0,
+                     const uint64_t* seeds, int32_t* ci, double* q, int32_t* info, void* stream);
+int wc_graph_agreement(int B, int R, int N, const int32_t* ci, double* D, void* stream);
+
 /* Dynamic functional connectivity (wc_fcd.hip): sliding-window FC with its FCD matrix (Hansen et al.
  * 2015) and the phase-coherence FCD (Deco & Kringelbach 2016).  The reference computes neither; these
  * definitions are the contract (tests/fcd_reference.py restates them in numpy).

@@ -9,10 +9,17 @@ on the device through sigchain.graph_measures, for one matrix or a [B, N, N]
 stack; betweenness_wei and betweenness_bin through sigchain.graph_betweenness,
 participation_coef and module_degree_zscore through
 sigchain.graph_module_measures (which also gives the modularity Q of a given
-partition).  torch and the library are imported on first use, so importing this
-module stays light.  The rest of the 2,600-line toolbox (partition search by
-Louvain, Newman and consensus, rich club, assortativity, signed and null-model
-variants) is analysis outside the sweep path.
+partition); community_louvain, agreement and get_agreement_matrix through
+sigchain.graph_louvain, graph_agreement and graph_consensus_matrix.  torch and
+the library are imported on first use, so importing this module stays light.
+
+Of the partition search, outside: the 'negative_sym' and 'negative_asym'
+objectives (unreachable in the reference, which refuses negative weights
+first), modularity_louvain_und_sign, consensus_und (it calls that unseeded
+signed variant), the spectral search of modularity_und (its kci form is
+graph_module_measures' Q), and N > 96.  The rest of the 2,600-line toolbox
+(rich club, assortativity, signed and null-model variants) is analysis outside
+the sweep path.
 """
 import numpy as np
 
@@ -222,3 +229,90 @@ def module_degree_zscore(W, ci, flag=0):
         raise ValueError(f"module_degree_zscore: flag {flag!r}, must be 0, 1, 2 or 3")
     lab, K = _labels("module_degree_zscore", ci, a)
     return _modules(a, lab, K, "zscore", zflag=int(flag))
+
+
+# ---- partition search on the device (sigchain.graph_louvain, graph_agreement, graph_consensus_matrix) ----
+
+def _louvain_args(name, W, ci, B):
+    """(W checked, starting labels or None, the objective as sigchain.graph_louvain takes it), refused
+    here where the reference refuses."""
+    a = _matrices(name, W, False)
+    if a.min() < -1e-10:                                         # graph_utils.py:999
+        raise ValueError(f"{name}: adjmat must not contain negative weights")
+    lab = None if ci is None else _labels(name, ci, a)[0]
+    if isinstance(B, str):
+        if B in ("negative_sym", "negative_asym"):
+            raise ValueError(f"{name}: B = {B!r} is not built: the reference refuses negative weights before it "
+                             "reaches that objective")
+        if B not in ("modularity", "potts"):
+            raise ValueError(f"{name}: unknown objective function type {B!r}, must be 'modularity', 'potts' or a matrix")
+        if B == "potts" and not ((a == 0) | (a == 1)).all():
+            raise ValueError(f"{name}: Potts hamiltonian requires binary input matrix")
+        return a, lab, B
+    obj = np.ascontiguousarray(B, dtype=np.float64)
+    if obj.shape != a.shape and obj.shape != a.shape[-2:]:
+        raise ValueError(f"{name}: objective function matrix does not match size of adjacency matrix")
+    return a, lab, obj
+
+
+def _to_device(x):
+    import torch
+    return torch.from_numpy(x).cuda() if isinstance(x, np.ndarray) else x
+
+
+def community_louvain(W, gamma=1, ci=None, B="modularity", seed=None):
+    """(ci, q): Louvain community structure of W and the objective reached (graph_utils.py:958-1122);
+    labels from 1.  B 'modularity', 'potts' or an objective matrix (symmetrised with a warning where
+    it is not symmetric); ci the starting partition; seed None draws one from os.urandom.  W is an
+    N x N matrix or a [B, N, N] stack (ci [B, N], q [B]; one launch).
+
+    The algorithm is the reference's; the order in which a sweep visits the nodes is the engine's
+    (Philox words keyed by the seed and the sweep's number, sigchain.graph_louvain), so a given seed
+    does NOT reproduce the partition numpy's generator gives for that seed, only the reference's
+    algorithm under the engine's order.  The same seed always gives the same result.
+    Not built: B 'negative_sym' and 'negative_asym' (unreachable in the reference, which raises on
+    negative weights first), modularity_louvain_und_sign, consensus_und, modularity_und's spectral
+    search, N > 96."""
+    import os
+
+    from . import sigchain
+    a, lab, obj = _louvain_args("community_louvain", W, ci, B)
+    if seed is None:
+        seed = int.from_bytes(os.urandom(8), "little")
+    part, q = sigchain.graph_louvain(_to_device(a), seeds=int(seed), gamma=float(gamma),
+                                     ci=None if lab is None else _to_device(lab), objective=_to_device(obj))
+    part, q = part.cpu().numpy().astype(np.int64) + 1, q.cpu().numpy()
+    return (part, float(q)) if a.ndim == 2 else (part, q)
+
+
+def agreement(ci, buffsz=1000):
+    """Agreement matrix D of the partitions ci [N, M], one per column, the reference's orientation
+    (graph_utils.py:890-932): D[i, j] partitions put i and j together; 0 on the diagonal.  A
+    [B, N, M] stack gives [B, N, N].  buffsz is accepted and ignored."""
+    import torch
+
+    from . import sigchain
+    c = np.asarray(ci)
+    if c.ndim not in (2, 3) or c.shape[-1] == 0:
+        raise ValueError(f"agreement: ci needs [vertex x partition], or a [B, N, M] stack, got shape {c.shape}")
+    if c.shape[-2] < 2 or c.shape[-2] > GRAPH_MAX_N:
+        raise ValueError(f"agreement: N = {c.shape[-2]}, the device kernels take 2 <= N <= {GRAPH_MAX_N}")
+    lab = np.unique(c, return_inverse=True)[1].reshape(c.shape).astype(np.int32)   # any labels: equality is kept
+    lab = np.ascontiguousarray(np.swapaxes(lab, -1, -2))
+    return sigchain.graph_agreement(torch.from_numpy(lab).cuda()).cpu().numpy()
+
+
+def get_agreement_matrix(W, reps=100, tau=0.5, gamma=1, ci=None, B="modularity", seeds=None):
+    """Thresholded agreement of reps Louvain runs (graph_utils.py:935-956): seeds 0 .. reps-1, the
+    agreement divided by reps, entries below tau set to 0, diagonal 0.  The reference cannot run with
+    seeds given (it reads seed_vector before assigning it); this accepts a sequence of length reps.
+    W is an N x N matrix or a [B, N, N] stack.  The visiting order is the engine's: see
+    community_louvain."""
+    from . import sigchain
+    a, lab, obj = _louvain_args("get_agreement_matrix", W, ci, B)
+    if seeds is not None and (np.ndim(seeds) != 1 or len(seeds) != reps):
+        raise ValueError("get_agreement_matrix: seeds must be an array of length equal to reps, or None")
+    D = sigchain.graph_consensus_matrix(_to_device(a), reps=int(reps), tau=float(tau), gamma=float(gamma),
+                                        ci=None if lab is None else _to_device(lab), objective=_to_device(obj),
+                                        seeds=None if seeds is None else [int(v) for v in seeds])
+    return D.cpu().numpy()

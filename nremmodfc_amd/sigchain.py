@@ -15,6 +15,7 @@ from __future__ import annotations
 
 import ctypes
 import functools
+import warnings
 
 import numpy as np
 import torch
@@ -484,6 +485,162 @@ def graph_module_measures(w, ci, measures=GRAPH_MODULE_MEASURES, degree="undirec
                                            float(gamma), _lib.ptr(res["participation"]), _lib.ptr(res["zscore"]),
                                            _lib.ptr(res["modularity"]), _lib.stream_handle()), "wc_graph_modules")
     return {m: (res[m][0] if single else res[m]) for m in names}
+
+
+GRAPH_LOUVAIN_OBJECTIVES = ("modularity", "potts")    # graph_louvain's built-in objectives; or a tensor
+GRAPH_PARTITION_SEARCH = ("graph_louvain", "graph_agreement", "graph_consensus_matrix")  # wc_louvain.hip
+GRAPH_LOUVAIN_MIN_WEIGHT = -1e-10                     # graph_utils.py:999: anything below is refused
+
+
+def _louvain_seeds(name, seeds):
+    """(host uint64 array [R], scalar) of an int or a sequence of ints in [0, 2^64)."""
+    scalar = isinstance(seeds, (int, np.integer)) and not isinstance(seeds, bool)
+    vals = [seeds] if scalar else (list(seeds) if isinstance(seeds, (list, tuple, range, np.ndarray)) else None)
+    if not vals or any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) < 1 << 64
+                       for v in vals):
+        raise ValueError(f"{name}: seeds must be an int or a non-empty sequence of ints in [0, 2^64), got {seeds!r}")
+    return np.array([int(v) for v in vals], dtype=np.uint64), scalar
+
+
+def _louvain_labels(name, ci, B, N, dev):
+    """Starting labels [N] or [B][N] (any integers) -> int32 [B][N] in [0, N), dense in the order of
+    the sorted distinct values of each row (np.unique's inverse), on the device and without a sync."""
+    if not isinstance(ci, torch.Tensor):
+        ci = torch.from_numpy(np.ascontiguousarray(np.asarray(ci)))
+    if ci.dtype not in (torch.int32, torch.int64, torch.int16, torch.int8, torch.uint8) or ci.dim() not in (1, 2) \
+            or ci.shape[-1] != N or (ci.dim() == 2 and ci.shape[0] != B):
+        raise TypeError(f"{name}: ci must hold integer labels, [N] or [B][N] with N = {N}, B = {B}")
+    ci = ci.to(dev).long()
+    ci = ci.expand(B, N) if ci.dim() == 1 else ci
+    srt, idx = ci.sort(dim=1, stable=True)
+    rank = torch.zeros_like(srt)
+    rank[:, 1:] = (srt[:, 1:] != srt[:, :-1]).cumsum(1)
+    return torch.empty_like(rank).scatter_(1, idx, rank).int().contiguous()
+
+
+def _halving_sum(x):
+    """Sum over the last axis by halving it with elementwise adds: torch's own reductions choose their
+    order by the shape, so a matrix would sum to other bits alone than inside a batch."""
+    n = x.shape[-1]
+    while n > 1:
+        h = (n + 1) // 2
+        top = x[..., :n - h] + x[..., h:n]
+        x = top if n == 2 * h else torch.cat([top, x[..., n - h:h]], dim=-1)
+        n = h
+    return x[..., 0]
+
+
+def graph_louvain(w, seeds=0, gamma=1.0, ci=None, objective="modularity", want_info=False):
+    """Louvain community search on the device (wc_graph_louvain; the reference's community_louvain):
+    w [B][N][N] or [N][N] fp64 device tensor, 2 <= N <= 96 -> (ci int32, q fp64), ci [B][R][N] with
+    labels 0 .. K-1 (the reference's minus 1) and q [B][R] the objective reached.  seeds is an int or
+    a sequence of R ints; an int gives no R axis, as an [N][N] input gives no batch axis.  Every
+    (matrix, seed) pair is an independent run in one launch.
+
+    objective "modularity": obj = W - gamma outer(rowsum, colsum) / s, s = sum W (Newman; Leicht &
+    Newman for a directed W); "potts": W - gamma (W == 0), W must be binary; or a [N][N] / [B][N][N]
+    fp64 tensor, used as it is (gamma is ignored) and symmetrised as (B + B^T) / 2, with a warning,
+    where it is not symmetric.  obj is built with torch ops on the device.  ci is None (every node its
+    own module) or starting labels, any integers, [N] for all matrices or [B][N].  A W with an entry
+    below -1e-10 raises ValueError, as the reference refuses it (this check and the Potts one read
+    one flag back from the device).
+
+    The algorithm is the reference's, decision for decision.  The visiting order is not numpy's:
+    sweep t of a run visits the nodes in the stable argsort of Philox4x32-10 words keyed by
+    (seed, t) (include/wcsde.h), so a seed does not reproduce the partition numpy gives for that
+    seed, only the reference's algorithm under that order; the same seed gives the same bits in
+    every call and every batch.  A matrix with a NaN or inf in obj or s has ci = -1 and q = NaN (so
+    has an empty graph under "modularity": s = 0; the reference returns the starting partition with
+    q = NaN there); so has a run that does not settle within 1000 sweeps of a level, where the
+    reference raises.  That happens on directed matrices at gamma > 1 (a node's gain is taken from its
+    row alone, and nodes then move in and out of modules without end); emptied modules keep rounding
+    residues of 1e-17 in Hnm there, between which a node may choose, so on a directed matrix at
+    gamma > 1 the device, which sums in another order than numpy, may take other turns than the
+    reference; everywhere else the tests find the reference's partition exactly.  want_info=True adds info int32 [B][R][2]: levels and node sweeps in all."""
+    name = "graph_louvain"
+    custom = isinstance(objective, torch.Tensor)
+    if not custom and (not isinstance(objective, str) or objective not in GRAPH_LOUVAIN_OBJECTIVES):
+        raise ValueError(f"{name}: objective {objective!r}, must be one of {list(GRAPH_LOUVAIN_OBJECTIVES)} or a "
+                         "[N][N] / [B][N][N] fp64 device tensor (negative_sym and negative_asym are not built: "
+                         "the reference refuses negative weights before it reaches them)")
+    seed_arr, scalar = _louvain_seeds(name, seeds)
+    w, single, B, N = _graph_stack(name, w)
+    wb = w.reshape(B, N, N)
+    dev = w.device
+    if custom and (objective.dtype != torch.float64 or objective.dim() not in (2, 3)
+                   or tuple(objective.shape[-2:]) != (N, N) or (objective.dim() == 3 and objective.shape[0] != B)
+                   or objective.device != dev):
+        raise TypeError(f"{name}: an objective tensor must be fp64 [N][N] or [B][N][N] on w's device, N = {N}, B = {B}")
+    ci0 = None if ci is None else _louvain_labels(name, ci, B, N, dev)
+    refuse = wb.min() < GRAPH_LOUVAIN_MIN_WEIGHT
+    if not custom and objective == "potts":
+        refuse = torch.stack([refuse, ~((wb == 0) | (wb == 1) | wb.isnan()).all()])
+    refuse = refuse.reshape(-1).tolist()
+    if refuse[0]:
+        raise ValueError(f"{name}: w must not contain negative weights (an entry below -1e-10)")
+    if len(refuse) > 1 and refuse[1]:
+        raise ValueError(f"{name}: the Potts objective requires a binary w")
+    ko, ki = _halving_sum(wb), _halving_sum(wb.transpose(1, 2))     # row and column sums, [B][N]
+    s = _halving_sum(ko)
+    if custom:
+        obj = objective.expand(B, N, N)
+        close = torch.isclose(obj, obj.transpose(1, 2)).all(dim=2).all(dim=1)
+        if not bool(close.all()):
+            warnings.warn(f"{name}: objective function matrix not symmetric, symmetrizing", stacklevel=2)
+            obj = torch.where(close[:, None, None], obj, (obj + obj.transpose(1, 2)) / 2)
+    elif objective == "modularity":
+        obj = wb - float(gamma) * (ko[:, :, None] * ki[:, None, :]) / s[:, None, None]
+    else:
+        obj = wb - float(gamma) * (wb == 0).to(torch.float64)
+    obj = obj.contiguous()
+    R = len(seed_arr)
+    seeds_dev = torch.from_numpy(seed_arr.view(np.int64)).to(dev)
+    out = torch.empty((B, R, N), dtype=torch.int32, device=dev)
+    q = torch.empty((B, R), dtype=torch.float64, device=dev)
+    info = torch.empty((B, R, 2), dtype=torch.int32, device=dev) if want_info else None
+    _lib.check(_lib.lib().wc_graph_louvain(B, R, N, _lib.ptr(obj), _lib.ptr(s), _lib.ptr(ci0), _lib.ptr(seeds_dev),
+                                           _lib.ptr(out), _lib.ptr(q), _lib.ptr(info), _lib.stream_handle()),
+               "wc_graph_louvain")
+    res = [out, q] + ([info] if want_info else [])
+    if scalar:
+        res = [t[:, 0] for t in res]
+    if single:
+        res = [t[0] for t in res]
+    return tuple(res)
+
+
+def graph_agreement(ci):
+    """Agreement matrix of R partitions on the device (wc_graph_agreement; the reference's agreement):
+    ci int32 device tensor [B][R][N] or [R][N] (graph_louvain's layout) -> D fp64 [B][N][N] or [N][N],
+    the number of the R partitions in which i and j share a label, exact, 0 on the diagonal.  A
+    negative label (a run that graph_louvain refused) makes its matrix's D NaN."""
+    if not isinstance(ci, torch.Tensor) or ci.dtype != torch.int32 or ci.dim() not in (2, 3):
+        raise TypeError("graph_agreement: ci must be an int32 device tensor [B][R][N] or [R][N]")
+    single = ci.dim() == 2
+    B, (R, N) = (1 if single else ci.shape[0]), ci.shape[-2:]
+    if N < 2 or N > GRAPH_MAX_N or B < 1 or R < 1:
+        raise ValueError(f"graph_agreement: N = {N}, R = {R}, B = {B}: needs B, R >= 1 and 2 <= N <= {GRAPH_MAX_N}")
+    ci = ci.contiguous()
+    D = torch.empty((B, N, N), dtype=torch.float64, device=ci.device)
+    _lib.check(_lib.lib().wc_graph_agreement(B, R, N, _lib.ptr(ci), _lib.ptr(D), _lib.stream_handle()),
+               "wc_graph_agreement")
+    return D[0] if single else D
+
+
+def graph_consensus_matrix(w, reps=100, tau=0.5, gamma=1.0, ci=None, objective="modularity", seeds=None):
+    """Thresholded agreement of reps Louvain runs on the device (the reference's get_agreement_matrix):
+    graph_louvain with seeds 0 .. reps-1 (or the reps seeds given), graph_agreement, D / reps, entries
+    below tau set to 0, the diagonal 0 -> [B][N][N] or [N][N].  One Louvain launch and one agreement
+    launch serve the whole stack.  A matrix that graph_louvain refuses is NaN throughout."""
+    if isinstance(reps, bool) or not isinstance(reps, (int, np.integer)) or reps < 1:
+        raise ValueError(f"graph_consensus_matrix: reps = {reps!r}, must be a positive int")
+    if seeds is None:
+        seeds = range(int(reps))
+    elif isinstance(seeds, (int, np.integer)) or len(seeds) != reps:
+        raise ValueError("graph_consensus_matrix: seeds must be a sequence of length reps, or None")
+    part, _ = graph_louvain(w, seeds=list(seeds), gamma=gamma, ci=ci, objective=objective)
+    D = graph_agreement(part) / int(reps)
+    return torch.where(D < float(tau), torch.zeros_like(D), D)
 
 
 FCD_MAX_N = 96           # wc_fcd, wc_fcd_phase: one window's correlation matrix, a tile's phasors per workgroup
