@@ -251,7 +251,7 @@ __device__ __forceinline__ void bs_split(const d2* zg, const d2* w, int n, int e
 
 // f(std::integral_constant<int, LOGN>) for LOGN = logL, 6 .. 13
 template <class F>
-hipError_t bs_dispatch(int logL, F&& f) {
+int bs_dispatch(int logL, F&& f) {
     switch (logL) {
         case 6: return f(std::integral_constant<int, 6>{});
         case 7: return f(std::integral_constant<int, 7>{});
@@ -264,14 +264,13 @@ hipError_t bs_dispatch(int logL, F&& f) {
     }
 }
 
-// a kernel of BsShape<LOGN>: its dynamic LDS allowed, then launched
+// a kernel of BsShape<LOGN>: its dynamic LDS allowed, then launched; who names the entry point
 template <int LOGN, class... P, class... A>
-hipError_t bs_launch(void (*kern)(P...), dim3 grid, hipStream_t st, const A&... args) {
+int bs_launch(const char* who, void (*kern)(P...), dim3 grid, hipStream_t st, const A&... args) {
     constexpr size_t lds = BsShape<LOGN>::lds_bytes;
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
+    if (int rc = wc_raise_lds(who, kern, lds)) return rc;
     hipLaunchKernelGGL(kern, grid, dim3(kThreads), lds, st, args...);
-    return hipSuccess;
+    return WC_OK;
 }
 
 // workgroups (x = groups of G columns, y) of a transform kernel
@@ -300,12 +299,12 @@ inline BsTables bs_layout(int n, void* ws) {
     return t;
 }
 
-inline hipError_t bs_fill_tables(const BsTables& t, int n, hipStream_t st) {
+inline int bs_fill_tables(const char* who, const BsTables& t, int n, hipStream_t st) {
     hipLaunchKernelGGL(bs_twiddle_kernel<kTwG>, dim3(kTwG / 256), dim3(256), 0, st, t.T);
     hipLaunchKernelGGL(bs_chirp_kernel<int>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, t.w);
     return bs_dispatch(t.logL, [&](auto I) {
         constexpr int LOGN = decltype(I)::value;
-        return bs_launch<LOGN>(bs_chirp_spectrum_kernel<LOGN>, dim3(1), st, n, (const d2*)t.T, (const d2*)t.w, t.Bf);
+        return bs_launch<LOGN>(who, bs_chirp_spectrum_kernel<LOGN>, dim3(1), st, n, (const d2*)t.T, (const d2*)t.w, t.Bf);
     });
 }
 
@@ -317,24 +316,18 @@ inline bool bs_shape_ok(int64_t C, int64_t T, int n, int noverlap) {
 // the arguments every Welch-family entry point takes; who names it and oname its output in the message
 inline int bs_check_args(const char* who, const char* oname, int64_t C, int64_t T, const double* x, int n, int noverlap,
                          const double* window, int detrend, double scale, const double* out, const void* workspace) {
-    char msg[200];
-    int code = WC_EINVAL;
-    if (C <= 0) snprintf(msg, sizeof msg, "%s: C <= 0", who);
-    else if (n < 2) snprintf(msg, sizeof msg, "%s: nperseg < 2", who);
-    else if (noverlap < 0 || noverlap >= n) snprintf(msg, sizeof msg, "%s: noverlap outside 0 .. nperseg - 1", who);
-    else if (T < n) snprintf(msg, sizeof msg, "%s: T < nperseg", who);
-    else if (!x || !window || !out) snprintf(msg, sizeof msg, "%s: x, window or %s is NULL", who, oname);
-    else if (detrend != 0 && detrend != 1) snprintf(msg, sizeof msg, "%s: detrend must be 0 (none) or 1 (constant)", who);
-    else if (!(scale > 0.0) || !isfinite(scale)) snprintf(msg, sizeof msg, "%s: scale must be finite and positive", who);
-    else if ((T - n) / (n - noverlap) >= INT32_MAX) snprintf(msg, sizeof msg, "%s: 2^31 segments or more", who);
-    else if (n > kMaxN) {
-        code = WC_EUNSUPPORTED;
-        snprintf(msg, sizeof msg, "%s: nperseg = %d > 4096 (the Bluestein FFT of 8192 points fills the LDS)", who, n);
-    } else if (((uintptr_t)x & 7) || ((uintptr_t)out & 7) || ((uintptr_t)window & 7))
-        snprintf(msg, sizeof msg, "%s: x, window and %s must be 8-byte aligned", who, oname);
-    else if ((uintptr_t)workspace & 15) snprintf(msg, sizeof msg, "%s: workspace must be 16-byte aligned", who);
-    else return WC_OK;
-    return wc_set_err(code, msg);
+    if (C <= 0) return wc_fail(WC_EINVAL, "%s: C <= 0", who);
+    if (n < 2) return wc_fail(WC_EINVAL, "%s: nperseg < 2", who);
+    if (noverlap < 0 || noverlap >= n) return wc_fail(WC_EINVAL, "%s: noverlap outside 0 .. nperseg - 1", who);
+    if (T < n) return wc_fail(WC_EINVAL, "%s: T < nperseg", who);
+    if (!x || !window || !out) return wc_fail(WC_EINVAL, "%s: x, window or %s is NULL", who, oname);
+    if (detrend != 0 && detrend != 1) return wc_fail(WC_EINVAL, "%s: detrend must be 0 (none) or 1 (constant)", who);
+    if (!(scale > 0.0) || !isfinite(scale)) return wc_fail(WC_EINVAL, "%s: scale must be finite and positive", who);
+    if ((T - n) / (n - noverlap) >= INT32_MAX) return wc_fail(WC_EINVAL, "%s: 2^31 segments or more", who);
+    if (n > kMaxN)
+        return wc_fail(WC_EUNSUPPORTED, "%s: nperseg = %d > 4096 (the Bluestein FFT of 8192 points fills the LDS)", who, n);
+    const WcSpan all[4] = {{"x", x, 0, 8}, {oname, out, 0, 8}, {"window", window, 0, 8}, {"workspace", workspace, 0, 16}};
+    return wc_check_align(who, all, 4);
 }
 #endif  // WC_BLUESTEIN_FFT_ONLY
 

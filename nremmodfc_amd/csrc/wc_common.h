@@ -26,3 +26,4 @@ inline int wc_hip_check(const char* what) {
     }
     return WC_OK;
 }
+#include "wc_args.h"  // the argument checks of the entry points

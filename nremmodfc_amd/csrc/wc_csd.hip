@@ -272,32 +272,24 @@ size_t wc_csd_workspace_size(int64_t C, int64_t T, int nperseg, int noverlap) {
 int wc_csd(int64_t C, int64_t T, const double* x, int nperseg, int noverlap, const double* window, int detrend,
            double scale, int mode, double* out, void* workspace, size_t ws_bytes, void* stream) {
     wc_clear_err();
-    char msg[200];
+    const char* fn = "wc_csd";
     const int n = nperseg;
-    if (C > kMaxC) return wc_set_err(WC_EINVAL, "wc_csd: C > 2^24");
-    if (int rc = bs_check_args("wc_csd", "out", C, T, x, n, noverlap, window, detrend, scale, out, workspace)) return rc;
+    if (C > kMaxC) return wc_fail(WC_EINVAL, "wc_csd: C > 2^24");
+    if (int rc = bs_check_args(fn, "out", C, T, x, n, noverlap, window, detrend, scale, out, workspace)) return rc;
     if (mode < WC_CSD_MATRIX || mode > WC_CSD_PAIR_COHERENCE)
-        return wc_set_err(WC_EINVAL, "wc_csd: unknown mode (WC_CSD_MATRIX .. WC_CSD_PAIR_COHERENCE)");
+        return wc_fail(WC_EINVAL, "wc_csd: unknown mode (WC_CSD_MATRIX .. WC_CSD_PAIR_COHERENCE)");
     const bool pairs = mode == WC_CSD_PAIRS || mode == WC_CSD_PAIR_COHERENCE;
     const bool coh = mode == WC_CSD_COHERENCE || mode == WC_CSD_PAIR_COHERENCE;
-    if (pairs && (C & 1)) return wc_set_err(WC_EINVAL, "wc_csd: a pair mode needs an even C (column i with i + C / 2)");
-    if (!pairs && C > kMaxMatC) {
-        snprintf(msg, sizeof msg, "wc_csd: C = %lld > 1024 columns in a matrix mode", (long long)C);
-        return wc_set_err(WC_EUNSUPPORTED, msg);
-    }
+    if (pairs && (C & 1)) return wc_fail(WC_EINVAL, "wc_csd: a pair mode needs an even C (column i with i + C / 2)");
+    if (!pairs && C > kMaxMatC)
+        return wc_fail(WC_EUNSUPPORTED, "wc_csd: C = %lld > 1024 columns in a matrix mode", (long long)C);
     const CsPlan p = cs_plan(C, T, n, noverlap, workspace);
     const int F = p.F;
-    {
-        const size_t cells = pairs ? (size_t)F * (size_t)(C / 2) : (size_t)F * (size_t)C * (size_t)C;
-        const uintptr_t x0 = (uintptr_t)x, x1 = x0 + (size_t)T * C * 8, p0 = (uintptr_t)out,
-                        p1 = p0 + cells * (coh ? 8 : 16);
-        if (p0 < x1 && x0 < p1) return wc_set_err(WC_EINVAL, "wc_csd: out must not alias x");
-    }
+    const size_t cells = pairs ? (size_t)F * (size_t)(C / 2) : (size_t)F * (size_t)C * (size_t)C;
+    const WcSpan in = {"x", x, (size_t)T * C * 8, 8}, o = {"out", out, cells * (coh ? 8 : 16), 8};
+    if (int rc = wc_check_alias(fn, &o, 1, &in, 1)) return rc;
     const size_t need = p.tab.bytes + p.aux + p.blk;
-    if (!workspace || ws_bytes < need) {
-        snprintf(msg, sizeof msg, "wc_csd: workspace < %zu bytes (wc_csd_workspace_size)", need);
-        return wc_set_err(WC_EWORKSPACE, msg);
-    }
+    if (int rc = wc_check_workspace(fn, "wc_csd_workspace_size", workspace, ws_bytes, need)) return rc;
 
     hipStream_t st = static_cast<hipStream_t>(stream);
     double* aux = reinterpret_cast<double*>(p.tab.Bf + ((size_t)1 << p.tab.logL));
@@ -307,19 +299,19 @@ int wc_csd(int64_t C, int64_t T, const double* x, int nperseg, int noverlap, con
     const int cpairs = (int)std::min<int64_t>(
         std::min<int64_t>((int64_t)((ws_bytes - p.tab.bytes - p.aux) / p.blk), all_pairs), kMaxChunkPairs);
 
-    hipError_t e = bs_fill_tables(p.tab, n, st);
+    int rc = bs_fill_tables(fn, p.tab, n, st);
     CsArgs a{C, n, n - noverlap, p.nseg, 0, detrend, x, window, p.tab.T, p.tab.w, p.tab.Bf, spec};
     const double mult = scale / (double)p.nseg;
     const int nt = (int)((C + kTile - 1) / kTile);
-    for (int64_t s0 = 0; s0 < p.nseg && e == hipSuccess; s0 += 2 * (int64_t)cpairs) {
+    for (int64_t s0 = 0; s0 < p.nseg && rc == WC_OK; s0 += 2 * (int64_t)cpairs) {
         const int cs = (int)std::min<int64_t>(2 * (int64_t)cpairs, p.nseg - s0);
         const int first = s0 == 0, last = s0 + cs >= p.nseg;
         a.s0 = (int)s0;
-        e = bs_dispatch(p.tab.logL, [&](auto I) {
+        rc = bs_dispatch(p.tab.logL, [&](auto I) {
             constexpr int LOGN = decltype(I)::value;
-            return bs_launch<LOGN>(cs_spec_kernel<LOGN>, bs_grid(LOGN, C, (cs + 1) / 2), st, a);
+            return bs_launch<LOGN>(fn, cs_spec_kernel<LOGN>, bs_grid(LOGN, C, (cs + 1) / 2), st, a);
         });
-        if (e != hipSuccess) break;
+        if (rc) break;
         if (pairs) {
             const int64_t tot = (int64_t)F * (C / 2);
             hipLaunchKernelGGL(cs_pair_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, C, F, n, cs, first,
@@ -329,16 +321,12 @@ int wc_csd(int64_t C, int64_t T, const double* x, int nperseg, int noverlap, con
                                (int)C, F, n, cs, first, last, (int)coh, mult, spec, out);
         }
     }
-    if (e == hipSuccess && mode == WC_CSD_COHERENCE) {
+    if (rc == WC_OK && mode == WC_CSD_COHERENCE) {
         const int64_t nd = (int64_t)F * C, tot = nd * C;
         hipLaunchKernelGGL(cs_diag_kernel, dim3((unsigned)((nd + 255) / 256)), dim3(256), 0, st, (int)C, F, out, aux);
         hipLaunchKernelGGL(cs_coherence_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, (int)C, F, aux,
                            out);
     }
-    if (e != hipSuccess) {
-        snprintf(wc_errbuf(), 512, "wc_csd: %s", hipGetErrorString(e));
-        return WC_EHIP;
-    }
-    return wc_hip_check("wc_csd");
+    return rc ? rc : wc_hip_check(fn);
 }
 

@@ -376,28 +376,19 @@ struct Shape {
 
 // Shapes and limits of wc_fcd; what == nullptr: no message (the workspace query).
 int check_shape(const char* what, int B, int N, int M, int win, int step, Shape* sh) {
-    char msg[200];
-    auto fail = [&](int code, const char* why) {
-        if (what) snprintf(msg, sizeof msg, "%s: %s", what, why), wc_set_err(code, msg);
-        return code;
-    };
-    if (B < 1) return fail(WC_EINVAL, "B < 1");
-    if (N < 3) return fail(WC_EINVAL, "N < 3 (a pattern needs at least 3 entries)");
-    if (N > kMaxN) return fail(WC_EUNSUPPORTED, "N > 96 (one window's correlation matrix per workgroup)");
-    if (win < 2) return fail(WC_EINVAL, "win < 2");
-    if (win > M) return fail(WC_EINVAL, "win > M");
-    if (step < 1) return fail(WC_EINVAL, "step < 1");
+    const char* fmt = what ? "%s: %s" : nullptr;
+    if (B < 1) return wc_fail(WC_EINVAL, fmt, what, "B < 1");
+    if (N < 3) return wc_fail(WC_EINVAL, fmt, what, "N < 3 (a pattern needs at least 3 entries)");
+    if (N > kMaxN) return wc_fail(WC_EUNSUPPORTED, fmt, what, "N > 96 (one window's correlation matrix per workgroup)");
+    if (win < 2) return wc_fail(WC_EINVAL, fmt, what, "win < 2");
+    if (win > M) return wc_fail(WC_EINVAL, fmt, what, "win > M");
+    if (step < 1) return wc_fail(WC_EINVAL, fmt, what, "step < 1");
     const int64_t nw = ((int64_t)M - win) / step + 1;
-    if (nw > WC_FCD_MAX_WINDOWS) return fail(WC_EUNSUPPORTED, "more than WC_FCD_MAX_WINDOWS = 4096 windows");
+    if (nw > WC_FCD_MAX_WINDOWS) return wc_fail(WC_EUNSUPPORTED, fmt, what, "more than WC_FCD_MAX_WINDOWS = 4096 windows");
     sh->nw = (int)nw;
     sh->P = N * (N - 1) / 2;
     sh->slot_doubles = (size_t)nw * sh->P + (size_t)nw;
     return WC_OK;
-}
-
-bool overlap(const void* a, size_t na, const void* b, size_t nb) {
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a0 < b0 + nb && b0 < a0 + na;
 }
 
 }  // namespace
@@ -414,24 +405,20 @@ int wc_fcd(int B, int N, int M, const double* x, int win, int step, double* fcd,
            size_t ws_bytes, void* stream) {
     wc_clear_err();
     Shape sh;
-    if (int rc = check_shape("wc_fcd", B, N, M, win, step, &sh)) return rc;
-    if (!x || !fcd) return wc_set_err(WC_EINVAL, "wc_fcd: x or fcd is NULL");
-    if (((uintptr_t)x | (uintptr_t)fcd | (uintptr_t)winfc | (uintptr_t)workspace) & 7)
-        return wc_set_err(WC_EINVAL, "wc_fcd: every pointer must be 8-byte aligned");
-    const size_t xb = sizeof(double) * (size_t)M * B * N, fb = sizeof(double) * (size_t)B * sh.nw * sh.nw;
-    const size_t wb = sizeof(double) * (size_t)B * sh.nw * sh.P;
-    if (overlap(x, xb, fcd, fb) || (winfc && (overlap(x, xb, winfc, wb) || overlap(fcd, fb, winfc, wb))))
-        return wc_set_err(WC_EINVAL, "wc_fcd: an output must not alias x or the other output");
+    const char* fn = "wc_fcd";
+    if (int rc = check_shape(fn, B, N, M, win, step, &sh)) return rc;
+    if (!x || !fcd) return wc_fail(WC_EINVAL, "wc_fcd: x or fcd is NULL");
+    const size_t b = (size_t)B, nw = (size_t)sh.nw;
+    const WcSpan ins[1] = {{"x", x, (size_t)M * b * N * 8, 8}};
+    const WcSpan outs[2] = {{"fcd", fcd, b * nw * nw * 8, 8}, {"winfc", winfc, b * nw * sh.P * 8, 8}};
+    const WcSpan wsp = {"workspace", workspace, ws_bytes, 8};
+    if (int rc = wc_check_align(fn, &wsp, 1)) return rc;
+    if (int rc = wc_check_spans(fn, ins, 1, outs, 2)) return rc;
     const size_t slot_bytes = sizeof(double) * sh.slot_doubles;
     const size_t need = slot_bytes * (size_t)(B < kMinSims ? B : kMinSims);
-    if (!workspace || ws_bytes < need) {
-        char msg[200];
-        snprintf(msg, sizeof msg, "wc_fcd: workspace NULL or %zu bytes < wc_fcd_workspace_size() = %zu", ws_bytes, need);
-        return wc_set_err(WC_EWORKSPACE, msg);
-    }
-    if (overlap(workspace, ws_bytes, x, xb) || overlap(workspace, ws_bytes, fcd, fb) ||
-        (winfc && overlap(workspace, ws_bytes, winfc, wb)))
-        return wc_set_err(WC_EINVAL, "wc_fcd: the workspace must not alias x or an output");
+    if (int rc = wc_check_workspace(fn, "wc_fcd_workspace_size", workspace, ws_bytes, need)) return rc;
+    if (int rc = wc_check_alias(fn, &wsp, 1, ins, 1)) return rc;
+    if (int rc = wc_check_alias(fn, &wsp, 1, outs, 2)) return rc;
 
     const int tiles_side = (sh.nw + kTile - 1) / kTile, tiles = tiles_side * (tiles_side + 1) / 2;
     size_t slots = ws_bytes / slot_bytes;  // >= min(B, kMinSims) >= 1
@@ -440,35 +427,32 @@ int wc_fcd(int B, int N, int M, const double* x, int win, int step, double* fcd,
     if (slots > (size_t)B) slots = (size_t)B;
     double* ws = static_cast<double*>(workspace);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    for (int b0 = 0; b0 < B; b0 += (int)slots) {
-        const int nb = B - b0 < (int)slots ? B - b0 : (int)slots;
+    wc_chunks(B, (int64_t)slots, [&](int64_t b0, int64_t nb) {
         hipLaunchKernelGGL(patterns_kernel, dim3((unsigned)nb * sh.nw), dim3(kThreads), 0, st, B, N, win, step, sh.nw,
-                           b0, x, ws, sh.slot_doubles, winfc);
+                           (int)b0, x, ws, sh.slot_doubles, winfc);
         hipLaunchKernelGGL(gram_kernel, dim3((unsigned)nb * tiles), dim3(kThreads), 0, st, sh.nw, sh.P, tiles_side,
                            tiles, ws, sh.slot_doubles, fcd + (size_t)b0 * sh.nw * sh.nw);
-    }
+    });
     return wc_hip_check("wc_fcd");
 }
 
 int wc_fcd_phase(int B, int N, int M, const double* phasor, double* fcd, void* stream) {
     wc_clear_err();
-    if (B < 1) return wc_set_err(WC_EINVAL, "wc_fcd_phase: B < 1");
-    if (N < 2) return wc_set_err(WC_EINVAL, "wc_fcd_phase: N < 2");
-    if (N > kMaxN) return wc_set_err(WC_EUNSUPPORTED, "wc_fcd_phase: N > 96 (a tile's phasors in one workgroup's LDS)");
-    if (M < 1) return wc_set_err(WC_EINVAL, "wc_fcd_phase: M < 1");
+    if (B < 1) return wc_fail(WC_EINVAL, "wc_fcd_phase: B < 1");
+    if (N < 2) return wc_fail(WC_EINVAL, "wc_fcd_phase: N < 2");
+    if (N > kMaxN) return wc_fail(WC_EUNSUPPORTED, "wc_fcd_phase: N > 96 (a tile's phasors in one workgroup's LDS)");
+    if (M < 1) return wc_fail(WC_EINVAL, "wc_fcd_phase: M < 1");
     if (M > WC_FCD_PHASE_MAX_M)
-        return wc_set_err(WC_EUNSUPPORTED, "wc_fcd_phase: M > WC_FCD_PHASE_MAX_M = 4096 samples");
-    if (!phasor || !fcd) return wc_set_err(WC_EINVAL, "wc_fcd_phase: phasor or fcd is NULL");
-    if (((uintptr_t)phasor | (uintptr_t)fcd) & 7)
-        return wc_set_err(WC_EINVAL, "wc_fcd_phase: every pointer must be 8-byte aligned");
-    if (overlap(phasor, sizeof(double) * 2 * (size_t)M * B * N, fcd, sizeof(double) * (size_t)B * M * M))
-        return wc_set_err(WC_EINVAL, "wc_fcd_phase: fcd must not alias phasor");
+        return wc_fail(WC_EUNSUPPORTED, "wc_fcd_phase: M > WC_FCD_PHASE_MAX_M = 4096 samples");
+    if (!phasor || !fcd) return wc_fail(WC_EINVAL, "wc_fcd_phase: phasor or fcd is NULL");
+    const WcSpan ins[1] = {{"phasor", phasor, (size_t)M * B * N * 16, 8}};
+    const WcSpan outs[1] = {{"fcd", fcd, (size_t)B * M * M * 8, 8}};
+    if (int rc = wc_check_spans("wc_fcd_phase", ins, 1, outs, 1)) return rc;
     const int tiles_side = (M + kPhaseTile - 1) / kPhaseTile, tiles = tiles_side * (tiles_side + 1) / 2;
     const int groups = (M + kGrid - 1) / kGrid;
     const int64_t per_launch = INT32_MAX / (tiles > groups ? tiles : groups);  // simulations whose workgroups fit a launch
     hipStream_t st = static_cast<hipStream_t>(stream);
-    for (int64_t b0 = 0; b0 < B; b0 += per_launch) {
-        const int64_t nb = B - b0 < per_launch ? B - b0 : per_launch;
+    wc_chunks(B, per_launch, [&](int64_t b0, int64_t nb) {
         double* out = fcd + (size_t)b0 * M * M;
         hipLaunchKernelGGL(phase_norms_kernel, dim3((unsigned)(nb * groups)), dim3(kThreads), 0, st, B, N, M, groups,
                            (int)b0, phasor, fcd);
@@ -476,7 +460,7 @@ int wc_fcd_phase(int B, int N, int M, const double* phasor, double* fcd, void* s
                            (int)b0, phasor, fcd);
         hipLaunchKernelGGL(phase_diagonal_kernel, dim3((unsigned)((nb * M + kThreads - 1) / kThreads)), dim3(kThreads), 0,
                            st, M, nb * M, out);
-    }
+    });
     return wc_hip_check("wc_fcd_phase");
 }
 

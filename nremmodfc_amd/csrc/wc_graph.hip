@@ -684,43 +684,20 @@ size_t modules_lds_bytes(int N) {
 }
 
 // ---- argument checks shared by the entry points ----
-struct Out {
-    const void* p;
-    size_t bytes;  // of the whole output
-};
-
-int check_args(const char* name, int B, int N, const double* w, const Out* outs, int nouts, bool per_node_grid) {
-    char msg[200];
-    if (B < 1) return snprintf(msg, sizeof msg, "%s: B < 1", name), wc_set_err(WC_EINVAL, msg);
-    if (N < 2) return snprintf(msg, sizeof msg, "%s: N < 2", name), wc_set_err(WC_EINVAL, msg);
-    if (N > kMaxN) {
-        snprintf(msg, sizeof msg, "%s: N = %d > 96 (one matrix per workgroup, in LDS)", name, N);
-        return wc_set_err(WC_EUNSUPPORTED, msg);
-    }
-    if (!w) return snprintf(msg, sizeof msg, "%s: w is NULL", name), wc_set_err(WC_EINVAL, msg);
+// shapes, w and at least one output; then w aligned, no output over w, every output aligned
+int check_graph(const char* fn, int B, int N, const WcSpan& w, const WcSpan* outs, int nouts, bool per_node_grid) {
+    if (B < 1) return wc_fail(WC_EINVAL, "%s: B < 1", fn);
+    if (N < 2) return wc_fail(WC_EINVAL, "%s: N < 2", fn);
+    if (N > kMaxN) return wc_fail(WC_EUNSUPPORTED, "%s: N = %d > 96 (one matrix per workgroup, in LDS)", fn, N);
+    if (!w.p) return wc_fail(WC_EINVAL, "%s: w is NULL", fn);
     if (per_node_grid && (int64_t)B * N > INT32_MAX)
-        return snprintf(msg, sizeof msg, "%s: 2^31 workgroups or more (B times N)", name), wc_set_err(WC_EINVAL, msg);
+        return wc_fail(WC_EINVAL, "%s: 2^31 workgroups or more (B times N)", fn);
     bool any = false;
     for (int k = 0; k < nouts; ++k) any = any || outs[k].p;
-    if (!any) return snprintf(msg, sizeof msg, "%s: every output is NULL", name), wc_set_err(WC_EINVAL, msg);
-    const uintptr_t w0 = (uintptr_t)w, w1 = w0 + (size_t)B * N * N * sizeof(double);
-    if (w0 & 7) return snprintf(msg, sizeof msg, "%s: w must be 8-byte aligned", name), wc_set_err(WC_EINVAL, msg);
-    for (int k = 0; k < nouts; ++k) {
-        if (!outs[k].p) continue;
-        const uintptr_t p0 = (uintptr_t)outs[k].p, p1 = p0 + outs[k].bytes;
-        if (p0 < w1 && w0 < p1)
-            return snprintf(msg, sizeof msg, "%s: an output must not alias w", name), wc_set_err(WC_EINVAL, msg);
-        if (p0 & 7)
-            return snprintf(msg, sizeof msg, "%s: every output must be 8-byte aligned", name), wc_set_err(WC_EINVAL, msg);
-    }
-    return WC_OK;
-}
-
-template <typename Kernel>
-int raise_lds(Kernel kernel, size_t lds) {
-    if (lds <= 65536) return WC_OK;
-    hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    return e == hipSuccess ? WC_OK : wc_set_err(WC_EHIP, hipGetErrorString(e));
+    if (!any) return wc_fail(WC_EINVAL, "%s: every output is NULL", fn);
+    if (int rc = wc_check_align(fn, &w, 1)) return rc;
+    if (int rc = wc_check_alias(fn, outs, nouts, &w, 1)) return rc;
+    return wc_check_align(fn, outs, nouts);
 }
 
 }  // namespace
@@ -730,75 +707,78 @@ extern "C" {
 int wc_graph_paths(int B, int N, const double* w, int lengths, int include_infinite, double* dist, int* hops,
                    double* stats, double* ecc, void* stream) {
     wc_clear_err();
+    const char* fn = "wc_graph_paths";
     const size_t b = B > 0 ? (size_t)B : 0, n = N > 0 ? (size_t)N : 0;
-    const Out outs[4] = {{dist, b * n * n * 8}, {hops, b * n * n * 4}, {stats, b * 4 * 8}, {ecc, b * n * 8}};
-    if (int rc = check_args("wc_graph_paths", B, N, w, outs, 4, false)) return rc;
+    const WcSpan outs[4] = {{"dist", dist, b * n * n * 8, 8}, {"hops", hops, b * n * n * 4, 8},
+                            {"stats", stats, b * 4 * 8, 8}, {"ecc", ecc, b * n * 8, 8}};
+    if (int rc = check_graph(fn, B, N, {"w", w, b * n * n * 8, 8}, outs, 4, false)) return rc;
     const size_t lds = paths_lds_bytes(N, hops != nullptr);
-    if (int rc = raise_lds(paths_kernel, lds)) return rc;
+    if (int rc = wc_raise_lds(fn, paths_kernel, lds)) return rc;
     hipLaunchKernelGGL(paths_kernel, dim3(B), dim3(kThreads), lds, static_cast<hipStream_t>(stream), N, w, lengths,
                        include_infinite, dist, hops, stats, ecc);
-    return wc_hip_check("wc_graph_paths");
+    return wc_hip_check(fn);
 }
 
 int wc_graph_local_efficiency(int B, int N, const double* w, double* eloc, void* stream) {
     wc_clear_err();
+    const char* fn = "wc_graph_local_efficiency";
     const size_t b = B > 0 ? (size_t)B : 0, n = N > 0 ? (size_t)N : 0;
-    const Out outs[1] = {{eloc, b * n * 8}};
-    if (int rc = check_args("wc_graph_local_efficiency", B, N, w, outs, 1, true)) return rc;
+    const WcSpan outs[1] = {{"eloc", eloc, b * n * 8, 8}};
+    if (int rc = check_graph(fn, B, N, {"w", w, b * n * n * 8, 8}, outs, 1, true)) return rc;
     const size_t lds = local_efficiency_lds_bytes(N);
-    if (int rc = raise_lds(local_efficiency_kernel, lds)) return rc;
+    if (int rc = wc_raise_lds(fn, local_efficiency_kernel, lds)) return rc;
     hipLaunchKernelGGL(local_efficiency_kernel, dim3((unsigned)(B * N)), dim3(kThreads), lds,
                        static_cast<hipStream_t>(stream), N, w, eloc);
-    return wc_hip_check("wc_graph_local_efficiency");
+    return wc_hip_check(fn);
 }
 
 int wc_graph_clustering(int B, int N, const double* w, double* clustering, double* transitivity, double* strengths,
                         int* degrees, void* stream) {
     wc_clear_err();
+    const char* fn = "wc_graph_clustering";
     const size_t b = B > 0 ? (size_t)B : 0, n = N > 0 ? (size_t)N : 0;
-    const Out outs[4] = {{clustering, b * n * 8}, {transitivity, b * 8}, {strengths, b * n * 8},
-                         {degrees, b * n * 4}};
-    if (int rc = check_args("wc_graph_clustering", B, N, w, outs, 4, false)) return rc;
+    const WcSpan outs[4] = {{"clustering", clustering, b * n * 8, 8}, {"transitivity", transitivity, b * 8, 8},
+                            {"strengths", strengths, b * n * 8, 8}, {"degrees", degrees, b * n * 4, 8}};
+    if (int rc = check_graph(fn, B, N, {"w", w, b * n * n * 8, 8}, outs, 4, false)) return rc;
     const size_t lds = clustering_lds_bytes(N);
-    if (int rc = raise_lds(clustering_kernel, lds)) return rc;
+    if (int rc = wc_raise_lds(fn, clustering_kernel, lds)) return rc;
     hipLaunchKernelGGL(clustering_kernel, dim3(B), dim3(kThreads), lds, static_cast<hipStream_t>(stream), N, w,
                        clustering, transitivity, strengths, degrees);
-    return wc_hip_check("wc_graph_clustering");
+    return wc_hip_check(fn);
 }
 
 int wc_graph_betweenness(int B, int N, const double* w, int lengths, double* bc, void* stream) {
     wc_clear_err();
+    const char* fn = "wc_graph_betweenness";
     const size_t b = B > 0 ? (size_t)B : 0, n = N > 0 ? (size_t)N : 0;
-    const Out outs[1] = {{bc, b * n * 8}};
-    if (int rc = check_args("wc_graph_betweenness", B, N, w, outs, 1, false)) return rc;
+    const WcSpan outs[1] = {{"bc", bc, b * n * 8, 8}};
+    if (int rc = check_graph(fn, B, N, {"w", w, b * n * n * 8, 8}, outs, 1, false)) return rc;
     const size_t lds = betweenness_lds_bytes(N);
-    if (int rc = raise_lds(betweenness_kernel, lds)) return rc;
+    if (int rc = wc_raise_lds(fn, betweenness_kernel, lds)) return rc;
     hipLaunchKernelGGL(betweenness_kernel, dim3(B), dim3(kBcThreads), lds, static_cast<hipStream_t>(stream), N, w,
                        lengths, bc);
-    return wc_hip_check("wc_graph_betweenness");
+    return wc_hip_check(fn);
 }
 
 int wc_graph_modules(int B, int N, int K, const double* w, const int32_t* ci, int degree, int zflag, double gamma,
                      double* part, double* z, double* q, void* stream) {
     wc_clear_err();
+    const char* fn = "wc_graph_modules";
     const size_t b = B > 0 ? (size_t)B : 0, n = N > 0 ? (size_t)N : 0;
-    const Out outs[3] = {{part, b * n * 8}, {z, b * n * 8}, {q, b * 8}};
-    if (int rc = check_args("wc_graph_modules", B, N, w, outs, 3, false)) return rc;
-    if (K < 1 || K > N) return wc_set_err(WC_EINVAL, "wc_graph_modules: K must be in [1, N]");
-    if (!ci) return wc_set_err(WC_EINVAL, "wc_graph_modules: ci is NULL");
-    if ((uintptr_t)ci & 3) return wc_set_err(WC_EINVAL, "wc_graph_modules: ci must be 4-byte aligned");
-    if (degree != 0 && degree != 1) return wc_set_err(WC_EINVAL, "wc_graph_modules: degree must be 0 (out) or 1 (in)");
-    if (zflag < 0 || zflag > 3) return wc_set_err(WC_EINVAL, "wc_graph_modules: zflag must be 0, 1, 2 or 3");
-    const uintptr_t c0 = (uintptr_t)ci, c1 = c0 + b * n * sizeof(int32_t);
-    for (const Out& o : outs) {
-        const uintptr_t p0 = (uintptr_t)o.p, p1 = p0 + o.bytes;
-        if (o.p && p0 < c1 && c0 < p1) return wc_set_err(WC_EINVAL, "wc_graph_modules: an output must not alias ci");
-    }
+    const WcSpan labels = {"ci", ci, b * n * 4, 4};
+    const WcSpan outs[3] = {{"part", part, b * n * 8, 8}, {"z", z, b * n * 8, 8}, {"q", q, b * 8, 8}};
+    if (int rc = check_graph(fn, B, N, {"w", w, b * n * n * 8, 8}, outs, 3, false)) return rc;
+    if (K < 1 || K > N) return wc_fail(WC_EINVAL, "wc_graph_modules: K must be in [1, N]");
+    if (!ci) return wc_fail(WC_EINVAL, "wc_graph_modules: ci is NULL");
+    if (int rc = wc_check_align(fn, &labels, 1)) return rc;
+    if (degree != 0 && degree != 1) return wc_fail(WC_EINVAL, "wc_graph_modules: degree must be 0 (out) or 1 (in)");
+    if (zflag < 0 || zflag > 3) return wc_fail(WC_EINVAL, "wc_graph_modules: zflag must be 0, 1, 2 or 3");
+    if (int rc = wc_check_alias(fn, outs, 3, &labels, 1)) return rc;
     const size_t lds = modules_lds_bytes(N);
-    if (int rc = raise_lds(modules_kernel, lds)) return rc;
+    if (int rc = wc_raise_lds(fn, modules_kernel, lds)) return rc;
     hipLaunchKernelGGL(modules_kernel, dim3(B), dim3(kThreads), lds, static_cast<hipStream_t>(stream), N, K, w, ci,
                        degree, zflag, gamma, part, z, q);
-    return wc_hip_check("wc_graph_modules");
+    return wc_hip_check(fn);
 }
 
 }  // extern "C"

@@ -185,44 +185,41 @@ __global__ void __launch_bounds__(kThreads) hl_row_kernel(const HlArgs a) {
 
 template <int N> constexpr size_t hl_lds_bytes() { return ((size_t)kPts + kPts / N + kTwLds) * sizeof(d2); }
 
+// who names the entry point in messages, here and below
 template <int LOGN, int MODE>
-hipError_t launch_col(const HlArgs& a, int64_t items, hipStream_t st) {
+int launch_col(const char* who, const HlArgs& a, int64_t items, hipStream_t st) {
     constexpr int N = 1 << LOGN;
     auto kern = hl_col_kernel<LOGN, MODE>;
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)hl_lds_bytes<N>());
-    if (e != hipSuccess) return e;
+    if (int rc = wc_raise_lds(who, kern, hl_lds_bytes<N>())) return rc;
     hipLaunchKernelGGL(kern, dim3((unsigned)(items / (kPts / N))), dim3(kThreads), hl_lds_bytes<N>(), st, a);
-    return hipSuccess;
+    return WC_OK;
 }
 template <int LOGN, bool CONV>
-hipError_t launch_row(const HlArgs& a, int64_t items, hipStream_t st) {
+int launch_row(const char* who, const HlArgs& a, int64_t items, hipStream_t st) {
     constexpr int N = 1 << LOGN;
     auto kern = hl_row_kernel<LOGN, CONV>;
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)hl_lds_bytes<N>());
-    if (e != hipSuccess) return e;
+    if (int rc = wc_raise_lds(who, kern, hl_lds_bytes<N>())) return rc;
     hipLaunchKernelGGL(kern, dim3((unsigned)(items / (kPts / N))), dim3(kThreads), hl_lds_bytes<N>(), st, a);
-    return hipSuccess;
+    return WC_OK;
 }
 
 template <int MODE>
-hipError_t col_pass(int log1, const HlArgs& a, hipStream_t st) {
+int col_pass(const char* who, int log1, const HlArgs& a, hipStream_t st) {
     const int64_t items = (int64_t)a.L2 * a.tc;  // a multiple of G: L2 >= 128 >= G
     switch (log1) {
-        case 8: return launch_col<8, MODE>(a, items, st);
-        case 9: return launch_col<9, MODE>(a, items, st);
-        default: return launch_col<10, MODE>(a, items, st);
+        case 8: return launch_col<8, MODE>(who, a, items, st);
+        case 9: return launch_col<9, MODE>(who, a, items, st);
+        default: return launch_col<10, MODE>(who, a, items, st);
     }
 }
 template <bool CONV>
-hipError_t row_pass(int log2, const HlArgs& a, hipStream_t st) {
+int row_pass(const char* who, int log2, const HlArgs& a, hipStream_t st) {
     const int64_t items = (int64_t)(a.L / a.L2) * a.tc;
     switch (log2) {
-        case 7: return launch_row<7, CONV>(a, items, st);
-        case 8: return launch_row<8, CONV>(a, items, st);
-        case 9: return launch_row<9, CONV>(a, items, st);
-        default: return launch_row<10, CONV>(a, items, st);
+        case 7: return launch_row<7, CONV>(who, a, items, st);
+        case 8: return launch_row<8, CONV>(who, a, items, st);
+        case 9: return launch_row<9, CONV>(who, a, items, st);
+        default: return launch_row<10, CONV>(who, a, items, st);
     }
 }
 
@@ -247,19 +244,14 @@ size_t wc_hilbert_long_workspace_size(int64_t C, int64_t M) {
 // with envelope, env [M][C]; `who` names the entry point in messages
 static int hl_run(const char* who, bool envelope, int64_t C, int64_t M, const double* x, double* out, void* workspace,
                   size_t ws_bytes, void* stream) {
-    char msg[200];
     const int logL = hl_log_len(M), log1 = (logL + 1) / 2, log2 = logL / 2;  // 8..10, 7..10
     const int64_t L = (int64_t)1 << logL;
     const size_t tab = hl_table_bytes(M, L), per_col = 2 * (size_t)L * sizeof(d2);
-    if (!workspace || ws_bytes < tab + per_col) {
-        snprintf(msg, sizeof msg, "%s: workspace < %zu bytes (%s)", who, tab + per_col,
-                 envelope ? "wc_hilbert_envelope_workspace_size" : "wc_hilbert_long_workspace_size");
-        return wc_set_err(WC_EWORKSPACE, msg);
-    }
-    if (((uintptr_t)workspace & 15) || ((uintptr_t)out & (envelope ? 7 : 15))) {  // d2 stores; env: doubles
-        snprintf(msg, sizeof msg, "%s: workspace%s must be 16-byte aligned", who, envelope ? "" : " and phasor");
-        return wc_set_err(WC_EINVAL, msg);
-    }
+    const char* size_fn = envelope ? "wc_hilbert_envelope_workspace_size" : "wc_hilbert_long_workspace_size";
+    if (int rc = wc_check_workspace(who, size_fn, workspace, ws_bytes, tab + per_col)) return rc;
+    const WcSpan al[2] = {{"workspace", workspace, 0, 16},  // d2 stores; env: doubles
+                          {envelope ? "env" : "phasor", out, 0, envelope ? 8 : 16}};
+    if (int rc = wc_check_align(who, al, 2)) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     d2* T = static_cast<d2*>(workspace);
     d2* w = T + kTwN;
@@ -270,37 +262,33 @@ static int hl_run(const char* who, bool envelope, int64_t C, int64_t M, const do
     hipLaunchKernelGGL(bs_twiddle_kernel<kTwN>, dim3(kTwN / 256), dim3(256), 0, st, T);
     hipLaunchKernelGGL(bs_chirp_kernel<int64_t>, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, st, M, w);
     HlArgs a{C, M, 0, 1, (int)L, 1 << log2, x, out, T, w, Bf, nullptr, buf0};
-    hipError_t e = col_pass<kColChirp>(log1, a, st);
+    int rc = col_pass<kColChirp>(who, log1, a, st);
     a.src = buf0;
-    if (e == hipSuccess) e = row_pass<false>(log2, a, st);
-    for (int64_t c0 = 0; c0 < C && e == hipSuccess; c0 += tcmax) {
+    if (rc == WC_OK) rc = row_pass<false>(who, log2, a, st);
+    for (int64_t c0 = 0; c0 < C && rc == WC_OK; c0 += tcmax) {
         a.c0 = c0;
         a.tc = (int)std::min<int64_t>(tcmax, C - c0);
         d2* buf1 = buf0 + (size_t)L * a.tc;
         a.src = nullptr, a.dst = buf0;
-        e = col_pass<kColFirst>(log1, a, st);
+        rc = col_pass<kColFirst>(who, log1, a, st);
         a.src = buf0, a.dst = buf1;
-        if (e == hipSuccess) e = row_pass<true>(log2, a, st);
+        if (rc == WC_OK) rc = row_pass<true>(who, log2, a, st);
         a.src = buf1, a.dst = buf0;
-        if (e == hipSuccess) e = col_pass<kColMid>(log1, a, st);
+        if (rc == WC_OK) rc = col_pass<kColMid>(who, log1, a, st);
         a.src = buf0, a.dst = buf1;
-        if (e == hipSuccess) e = row_pass<true>(log2, a, st);
+        if (rc == WC_OK) rc = row_pass<true>(who, log2, a, st);
         a.src = buf1, a.dst = nullptr;
-        if (e == hipSuccess) e = envelope ? col_pass<kColLastEnv>(log1, a, st) : col_pass<kColLast>(log1, a, st);
+        if (rc == WC_OK) rc = envelope ? col_pass<kColLastEnv>(who, log1, a, st) : col_pass<kColLast>(who, log1, a, st);
     }
-    if (e != hipSuccess) {
-        snprintf(wc_errbuf(), 512, "%s: %s", who, hipGetErrorString(e));
-        return WC_EHIP;
-    }
-    return wc_hip_check(who);
+    return rc ? rc : wc_hip_check(who);
 }
 
 int wc_hilbert_phase_long(int64_t C, int64_t M, const double* x, double* phasor, void* workspace, size_t ws_bytes,
                           void* stream) {
     wc_clear_err();
-    if (C <= 0 || M < 2 || !x || !phasor) return wc_set_err(WC_EINVAL, "wc_hilbert_phase_long: bad arguments");
+    if (C <= 0 || M < 2 || !x || !phasor) return wc_fail(WC_EINVAL, "wc_hilbert_phase_long: bad arguments");
     if (M > kMaxM)
-        return wc_set_err(WC_EUNSUPPORTED, "wc_hilbert_phase_long: M > 524288 (the FFT length 2^20 = 1024 x 1024)");
+        return wc_fail(WC_EUNSUPPORTED, "wc_hilbert_phase_long: M > 524288 (the FFT length 2^20 = 1024 x 1024)");
     return hl_run("wc_hilbert_phase_long", false, C, M, x, phasor, workspace, ws_bytes, stream);
 }
 

@@ -449,11 +449,10 @@ int wc_hma(int B, int N, double* fc, double* hin, double* hse, double* hin_node,
            double* sv, void* stream) {
     wc_clear_err();
     if (B <= 0 || N < 3 || !fc || !hin || !hse || !hin_node || !hse_node)
-        return wc_set_err(WC_EINVAL, "wc_hma: bad B/N or NULL output");
-    if (N > kMaxN) return wc_set_err(WC_EUNSUPPORTED, "wc_hma: N > 96 (F and V must fit in LDS)");
+        return wc_fail(WC_EINVAL, "wc_hma: bad B/N or NULL output");
+    if (N > kMaxN) return wc_fail(WC_EUNSUPPORTED, "wc_hma: N > 96 (F and V must fit in LDS)");
     const size_t lds = hma_lds_bytes(N);
-    hipError_t e = hipFuncSetAttribute((const void*)hma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return wc_set_err(WC_EHIP, hipGetErrorString(e));
+    if (int rc = wc_raise_lds("wc_hma", hma_kernel, lds)) return rc;
     hipLaunchKernelGGL(hma_kernel, dim3(B), dim3(kThreads), lds, static_cast<hipStream_t>(stream), N, fc, hin, hse,
                        hin_node, hse_node, clus_num, sv);
     return wc_hip_check("wc_hma");
@@ -463,14 +462,10 @@ int wc_hma_modes(int B, int N, const double* lam, const double* vt, double* hin,
                  double* hse_node, int* clus_num, double* sv, void* stream) {
     wc_clear_err();
     if (B <= 0 || N < 3 || !lam || !vt || !hin || !hse || !hin_node || !hse_node)
-        return wc_set_err(WC_EINVAL, "wc_hma_modes: bad B/N or NULL argument");
+        return wc_fail(WC_EINVAL, "wc_hma_modes: bad B/N or NULL argument");
     const size_t lds = hma_modes_lds_bytes(N);
-    if (lds > 160 * 1024) return wc_set_err(WC_EUNSUPPORTED, "wc_hma_modes: N too large for the LDS label arrays");
-    if (lds > 65536) {
-        hipError_t e = hipFuncSetAttribute((const void*)hma_modes_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)lds);
-        if (e != hipSuccess) return wc_set_err(WC_EHIP, hipGetErrorString(e));
-    }
+    if (lds > 160 * 1024) return wc_fail(WC_EUNSUPPORTED, "wc_hma_modes: N too large for the LDS label arrays");
+    if (int rc = wc_raise_lds("wc_hma_modes", hma_modes_kernel, lds)) return rc;
     hipLaunchKernelGGL(hma_modes_kernel, dim3(B), dim3(kThreads), lds, static_cast<hipStream_t>(stream), N, lam, vt,
                        hin, hse, hin_node, hse_node, clus_num, sv);
     return wc_hip_check("wc_hma_modes");

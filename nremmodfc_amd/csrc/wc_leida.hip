@@ -293,26 +293,17 @@ __global__ void __launch_bounds__(kThreads) state_stats_kernel(int b0, int B, in
     }
 }
 
-bool overlap(const void* a, size_t na, const void* b, size_t nb) {
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a0 < b0 + nb && b0 < a0 + na;
-}
-
 // Shapes and limits of the k-means entry points; what == nullptr: no message (the workspace query).
 int check_kmeans(const char* what, int64_t R, int N, int K, int metric) {
-    char msg[200];
-    auto fail = [&](int code, const char* why) {
-        if (what) snprintf(msg, sizeof msg, "%s: %s", what, why), wc_set_err(code, msg);
-        return code;
-    };
-    if (R < 1) return fail(WC_EINVAL, "R < 1");
-    if (R > WC_LEIDA_MAX_ROWS) return fail(WC_EUNSUPPORTED, "R > WC_LEIDA_MAX_ROWS = 2^40 rows");
-    if (N < 2) return fail(WC_EINVAL, "N < 2");
-    if (N > kMaxN) return fail(WC_EUNSUPPORTED, "N > 1024");
-    if (K < 1) return fail(WC_EINVAL, "K < 1");
-    if (K > kMaxK) return fail(WC_EUNSUPPORTED, "K > 32");
+    const char* fmt = what ? "%s: %s" : nullptr;
+    if (R < 1) return wc_fail(WC_EINVAL, fmt, what, "R < 1");
+    if (R > WC_LEIDA_MAX_ROWS) return wc_fail(WC_EUNSUPPORTED, fmt, what, "R > WC_LEIDA_MAX_ROWS = 2^40 rows");
+    if (N < 2) return wc_fail(WC_EINVAL, fmt, what, "N < 2");
+    if (N > kMaxN) return wc_fail(WC_EUNSUPPORTED, fmt, what, "N > 1024");
+    if (K < 1) return wc_fail(WC_EINVAL, fmt, what, "K < 1");
+    if (K > kMaxK) return wc_fail(WC_EUNSUPPORTED, fmt, what, "K > 32");
     if (metric != WC_KMEANS_SQEUCLIDEAN && metric != WC_KMEANS_COSINE)
-        return fail(WC_EINVAL, "unknown metric (WC_KMEANS_SQEUCLIDEAN or WC_KMEANS_COSINE)");
+        return wc_fail(WC_EINVAL, fmt, what, "unknown metric (WC_KMEANS_SQEUCLIDEAN or WC_KMEANS_COSINE)");
     return WC_OK;
 }
 
@@ -336,25 +327,22 @@ extern "C" {
 
 int wc_leida_eigvec(int64_t R, int N, const double* phasor, double* vec, double* share, void* stream) {
     wc_clear_err();
-    if (R < 1) return wc_set_err(WC_EINVAL, "wc_leida_eigvec: R < 1");
-    if (R > WC_LEIDA_MAX_ROWS) return wc_set_err(WC_EUNSUPPORTED, "wc_leida_eigvec: R > WC_LEIDA_MAX_ROWS = 2^40 rows");
-    if (N < 2) return wc_set_err(WC_EINVAL, "wc_leida_eigvec: N < 2");
-    if (N > kMaxN) return wc_set_err(WC_EUNSUPPORTED, "wc_leida_eigvec: N > 1024 (a row in one wave's registers)");
-    if (!phasor || !vec || !share) return wc_set_err(WC_EINVAL, "wc_leida_eigvec: phasor, vec or share is NULL");
-    if (((uintptr_t)phasor & 15) || (((uintptr_t)vec | (uintptr_t)share) & 7))
-        return wc_set_err(WC_EINVAL, "wc_leida_eigvec: phasor must be 16-byte aligned, vec and share 8-byte aligned");
-    const size_t pb = sizeof(double) * 2 * (size_t)R * N, vb = sizeof(double) * (size_t)R * N;
-    const size_t sb = sizeof(double) * (size_t)R;
-    if (overlap(phasor, pb, vec, vb) || overlap(phasor, pb, share, sb) || overlap(vec, vb, share, sb))
-        return wc_set_err(WC_EINVAL, "wc_leida_eigvec: an output must not alias phasor or the other output");
+    if (R < 1) return wc_fail(WC_EINVAL, "wc_leida_eigvec: R < 1");
+    if (R > WC_LEIDA_MAX_ROWS) return wc_fail(WC_EUNSUPPORTED, "wc_leida_eigvec: R > WC_LEIDA_MAX_ROWS = 2^40 rows");
+    if (N < 2) return wc_fail(WC_EINVAL, "wc_leida_eigvec: N < 2");
+    if (N > kMaxN) return wc_fail(WC_EUNSUPPORTED, "wc_leida_eigvec: N > 1024 (a row in one wave's registers)");
+    if (!phasor || !vec || !share) return wc_fail(WC_EINVAL, "wc_leida_eigvec: phasor, vec or share is NULL");
+    const size_t r = (size_t)R, n = (size_t)N;
+    const WcSpan ins[1] = {{"phasor", phasor, r * n * 16, 16}};
+    const WcSpan outs[2] = {{"vec", vec, r * n * 8, 8}, {"share", share, r * 8, 8}};
+    if (int rc = wc_check_spans("wc_leida_eigvec", ins, 1, outs, 2)) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const double2* z = reinterpret_cast<const double2*>(phasor);
     // N <= 128: 16 lanes a row, four rows a wave (shorter butterflies, four rows' loads in flight a wave)
     const int lanes = N <= kEigNarrowN ? kEigNarrow : kWave, rows_wg = kThreads / lanes;
     const int per = (N + lanes - 1) / lanes;
     const int64_t per_launch = kLaunchBlocks * rows_wg;
-    for (int64_t r0 = 0; r0 < R; r0 += per_launch) {
-        const int64_t nr = R - r0 < per_launch ? R - r0 : per_launch;
+    wc_chunks(R, per_launch, [&](int64_t r0, int64_t nr) {
         const dim3 grid((unsigned)((nr + rows_wg - 1) / rows_wg)), block(kThreads);
 #define WC_EIG(L, P) hipLaunchKernelGGL((eigvec_kernel<L, P>), grid, block, 0, st, r0, nr, N, z, vec, share)
         if (lanes == kEigNarrow) {
@@ -369,7 +357,7 @@ int wc_leida_eigvec(int64_t R, int N, const double* phasor, double* vec, double*
             else WC_EIG(kWave, 16);
         }
 #undef WC_EIG
-    }
+    });
     return wc_hip_check("wc_leida_eigvec");
 }
 
@@ -378,25 +366,20 @@ int wc_kmeans_assign(int64_t R, int N, int K, const double* x, const double* cen
     wc_clear_err();
     if (int rc = check_kmeans("wc_kmeans_assign", R, N, K, metric)) return rc;
     if (!x || !cent || !labels || !dist)
-        return wc_set_err(WC_EINVAL, "wc_kmeans_assign: x, cent, labels or dist is NULL");
-    if ((((uintptr_t)x | (uintptr_t)cent | (uintptr_t)dist) & 7) || ((uintptr_t)labels & 3))
-        return wc_set_err(WC_EINVAL, "wc_kmeans_assign: x, cent and dist must be 8-byte aligned, labels 4-byte aligned");
-    const size_t xb = sizeof(double) * (size_t)R * N, cb = sizeof(double) * (size_t)K * N;
-    const size_t lb = sizeof(int32_t) * (size_t)R, db = sizeof(double) * (size_t)R;
-    if (overlap(x, xb, labels, lb) || overlap(x, xb, dist, db) || overlap(cent, cb, labels, lb) ||
-        overlap(cent, cb, dist, db) || overlap(labels, lb, dist, db))
-        return wc_set_err(WC_EINVAL, "wc_kmeans_assign: an output must not alias an input or the other output");
+        return wc_fail(WC_EINVAL, "wc_kmeans_assign: x, cent, labels or dist is NULL");
+    const size_t r = (size_t)R, n = (size_t)N, k = (size_t)K;
+    const WcSpan ins[2] = {{"x", x, r * n * 8, 8}, {"cent", cent, k * n * 8, 8}};
+    const WcSpan outs[2] = {{"labels", labels, r * 4, 4}, {"dist", dist, r * 8, 8}};
+    if (int rc = wc_check_spans("wc_kmeans_assign", ins, 2, outs, 2)) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const int64_t per_launch = kLaunchBlocks * kAsgRows;
-    for (int64_t r0 = 0; r0 < R; r0 += per_launch) {
-        const int64_t nr = R - r0 < per_launch ? R - r0 : per_launch;
+    wc_chunks(R, kLaunchBlocks * kAsgRows, [&](int64_t r0, int64_t nr) {
         const dim3 grid((unsigned)((nr + kAsgRows - 1) / kAsgRows)), block(kThreads);
         if (metric == WC_KMEANS_SQEUCLIDEAN)
             hipLaunchKernelGGL(assign_kernel<WC_KMEANS_SQEUCLIDEAN>, grid, block, 0, st, r0, nr, N, K, x, cent, labels,
                                dist);
         else
             hipLaunchKernelGGL(assign_kernel<WC_KMEANS_COSINE>, grid, block, 0, st, r0, nr, N, K, x, cent, labels, dist);
-    }
+    });
     return wc_hip_check("wc_kmeans_assign");
 }
 
@@ -411,46 +394,32 @@ int wc_kmeans_update(int64_t R, int N, int K, const double* x, const int32_t* la
     wc_clear_err();
     if (int rc = check_kmeans("wc_kmeans_update", R, N, K, metric)) return rc;
     if (!x || !labels || !cent_prev || !cent || !count)
-        return wc_set_err(WC_EINVAL, "wc_kmeans_update: x, labels, cent_prev, cent or count is NULL");
-    if ((((uintptr_t)x | (uintptr_t)cent_prev | (uintptr_t)cent | (uintptr_t)count | (uintptr_t)workspace) & 7) ||
-        ((uintptr_t)labels & 3))
-        return wc_set_err(WC_EINVAL, "wc_kmeans_update: labels must be 4-byte aligned, every other pointer 8-byte aligned");
-    const size_t xb = sizeof(double) * (size_t)R * N, cb = sizeof(double) * (size_t)K * N;
-    const size_t lb = sizeof(int32_t) * (size_t)R, nb = sizeof(int64_t) * (size_t)K;
-    if (overlap(cent, cb, x, xb) || overlap(cent, cb, labels, lb) || overlap(cent, cb, cent_prev, cb) ||
-        overlap(count, nb, x, xb) || overlap(count, nb, labels, lb) || overlap(count, nb, cent_prev, cb) ||
-        overlap(cent, cb, count, nb))
-        return wc_set_err(WC_EINVAL, "wc_kmeans_update: an output must not alias an input or the other output");
+        return wc_fail(WC_EINVAL, "wc_kmeans_update: x, labels, cent_prev, cent or count is NULL");
+    const char* fn = "wc_kmeans_update";
+    const size_t r = (size_t)R, n = (size_t)N, k = (size_t)K;
+    const WcSpan ins[3] = {{"x", x, r * n * 8, 8}, {"labels", labels, r * 4, 4}, {"cent_prev", cent_prev, k * n * 8, 8}};
+    const WcSpan outs[2] = {{"cent", cent, k * n * 8, 8}, {"count", count, k * 8, 8}};
+    const WcSpan ws = {"workspace", workspace, ws_bytes, 8};
+    if (int rc = wc_check_align(fn, &ws, 1)) return rc;
+    if (int rc = wc_check_spans(fn, ins, 3, outs, 2)) return rc;
     const UpdateLayout u = update_layout(R, N, K, metric);
     const size_t need = u.part_bytes + u.cnt_bytes + u.norm_bytes;
-    if (!workspace || ws_bytes < need) {
-        char msg[200];
-        snprintf(msg, sizeof msg, "wc_kmeans_update: workspace NULL or %zu bytes < wc_kmeans_workspace_size() = %zu",
-                 ws_bytes, need);
-        return wc_set_err(WC_EWORKSPACE, msg);
-    }
-    if (overlap(workspace, ws_bytes, x, xb) || overlap(workspace, ws_bytes, labels, lb) ||
-        overlap(workspace, ws_bytes, cent_prev, cb) || overlap(workspace, ws_bytes, cent, cb) ||
-        overlap(workspace, ws_bytes, count, nb))
-        return wc_set_err(WC_EINVAL, "wc_kmeans_update: the workspace must not alias an input or an output");
+    if (int rc = wc_check_workspace(fn, "wc_kmeans_workspace_size", workspace, ws_bytes, need)) return rc;
+    if (int rc = wc_check_alias(fn, &ws, 1, ins, 3)) return rc;
+    if (int rc = wc_check_alias(fn, &ws, 1, outs, 2)) return rc;
     // the minimum is all that is ever used: the result cannot depend on what lies beyond it
     double* part = static_cast<double*>(workspace);
     int64_t* cnt = reinterpret_cast<int64_t*>(static_cast<char*>(workspace) + u.part_bytes);
     double* norms = u.norm_bytes ? reinterpret_cast<double*>(static_cast<char*>(workspace) + u.part_bytes + u.cnt_bytes)
                                  : nullptr;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (norms) {
-        const int64_t per_launch = kLaunchBlocks * kEigRows;
-        for (int64_t r0 = 0; r0 < R; r0 += per_launch) {
-            const int64_t nr = R - r0 < per_launch ? R - r0 : per_launch;
+    if (norms)
+        wc_chunks(R, kLaunchBlocks * kEigRows, [&](int64_t r0, int64_t nr) {
             hipLaunchKernelGGL(norms_kernel, dim3((unsigned)((nr + kEigRows - 1) / kEigRows)), dim3(kThreads), 0, st, r0,
                                nr, N, x, norms);
-        }
-    }
+        });
     const int tiles = (N + kWave - 1) / kWave;  // <= 16
-    const int64_t per_launch = kLaunchBlocks / 16;
-    for (int64_t b0 = 0; b0 < u.nblk; b0 += per_launch) {
-        const int64_t nbk = u.nblk - b0 < per_launch ? u.nblk - b0 : per_launch;
+    wc_chunks(u.nblk, kLaunchBlocks / 16, [&](int64_t b0, int64_t nbk) {
         const dim3 grid((unsigned)(nbk * tiles)), block(kWave);
         if (K <= 4)
             hipLaunchKernelGGL(update_partial_kernel<4>, grid, block, 0, st, b0, tiles, R, N, K, x, labels, norms, part, cnt);
@@ -462,7 +431,7 @@ int wc_kmeans_update(int64_t R, int N, int K, const double* x, const int32_t* la
         else
             hipLaunchKernelGGL(update_partial_kernel<32>, grid, block, 0, st, b0, tiles, R, N, K, x, labels, norms, part,
                                cnt);
-    }
+    });
     hipLaunchKernelGGL(update_final_kernel, dim3((unsigned)((K * N + kThreads - 1) / kThreads)), dim3(kThreads), 0, st,
                        u.nblk, N, K, part, cnt, cent_prev, cent, count);
     return wc_hip_check("wc_kmeans_update");
@@ -471,24 +440,22 @@ int wc_kmeans_update(int64_t R, int N, int K, const double* x, const int32_t* la
 int wc_state_stats(int B, int M, int K, const int32_t* labels, double* occupancy, double* dwell, double* trans,
                    void* stream) {
     wc_clear_err();
-    if (B < 1) return wc_set_err(WC_EINVAL, "wc_state_stats: B < 1");
-    if (M < 1) return wc_set_err(WC_EINVAL, "wc_state_stats: M < 1");
-    if (K < 1) return wc_set_err(WC_EINVAL, "wc_state_stats: K < 1");
-    if (K > kMaxK) return wc_set_err(WC_EUNSUPPORTED, "wc_state_stats: K > 32");
+    if (B < 1) return wc_fail(WC_EINVAL, "wc_state_stats: B < 1");
+    if (M < 1) return wc_fail(WC_EINVAL, "wc_state_stats: M < 1");
+    if (K < 1) return wc_fail(WC_EINVAL, "wc_state_stats: K < 1");
+    if (K > kMaxK) return wc_fail(WC_EUNSUPPORTED, "wc_state_stats: K > 32");
     if (!labels || !occupancy || !dwell || !trans)
-        return wc_set_err(WC_EINVAL, "wc_state_stats: labels, occupancy, dwell or trans is NULL");
-    if ((((uintptr_t)occupancy | (uintptr_t)dwell | (uintptr_t)trans) & 7) || ((uintptr_t)labels & 3))
-        return wc_set_err(WC_EINVAL, "wc_state_stats: labels must be 4-byte aligned, the outputs 8-byte aligned");
-    const size_t lb = sizeof(int32_t) * (size_t)M * B, ob = sizeof(double) * (size_t)B * K, tb = ob * K;
-    if (overlap(labels, lb, occupancy, ob) || overlap(labels, lb, dwell, ob) || overlap(labels, lb, trans, tb) ||
-        overlap(occupancy, ob, dwell, ob) || overlap(occupancy, ob, trans, tb) || overlap(dwell, ob, trans, tb))
-        return wc_set_err(WC_EINVAL, "wc_state_stats: an output must not alias labels or another output");
+        return wc_fail(WC_EINVAL, "wc_state_stats: labels, occupancy, dwell or trans is NULL");
+    const size_t b = (size_t)B, m = (size_t)M, k = (size_t)K;
+    const WcSpan ins[1] = {{"labels", labels, m * b * 4, 4}};
+    const WcSpan outs[3] = {{"occupancy", occupancy, b * k * 8, 8}, {"dwell", dwell, b * k * 8, 8},
+                            {"trans", trans, b * k * k * 8, 8}};
+    if (int rc = wc_check_spans("wc_state_stats", ins, 1, outs, 3)) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    for (int64_t b0 = 0; b0 < B; b0 += kLaunchBlocks) {
-        const int64_t nb = B - b0 < kLaunchBlocks ? B - b0 : kLaunchBlocks;
+    wc_chunks(B, kLaunchBlocks, [&](int64_t b0, int64_t nb) {
         hipLaunchKernelGGL(state_stats_kernel, dim3((unsigned)nb), dim3(kThreads), 0, st, (int)b0, B, M, K, labels,
                            occupancy, dwell, trans);
-    }
+    });
     return wc_hip_check("wc_state_stats");
 }
 

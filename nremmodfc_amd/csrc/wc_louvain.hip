@@ -273,54 +273,11 @@ __global__ void __launch_bounds__(kAgThreads) agreement_kernel(int R, int N, con
 }
 
 // ---- argument checks ----
-struct Span {
-    const char* name;
-    const void* p;
-    size_t bytes;  // of the whole array
-    int align;
-};
-
-// shapes first, then every pointer of ins and outs (a NULL ins[k] with bytes 0 is an optional one
-// left out), alignment, and no output overlapping an input or another output
-int check_spans(const char* fn, const Span* ins, int nins, const Span* outs, int nouts) {
-    char msg[200];
-    for (int pass = 0; pass < 2; ++pass) {
-        const Span* a = pass ? outs : ins;
-        for (int k = 0; k < (pass ? nouts : nins); ++k) {
-            if (!a[k].p) continue;
-            if ((uintptr_t)a[k].p & (a[k].align - 1)) {
-                snprintf(msg, sizeof msg, "%s: %s must be %d-byte aligned", fn, a[k].name, a[k].align);
-                return wc_set_err(WC_EINVAL, msg);
-            }
-        }
-    }
-    for (int o = 0; o < nouts; ++o) {
-        if (!outs[o].p) continue;
-        const uintptr_t p0 = (uintptr_t)outs[o].p, p1 = p0 + outs[o].bytes;
-        for (int pass = 0; pass < 2; ++pass) {
-            const Span* a = pass ? outs : ins;
-            for (int k = 0; k < (pass ? o : nins); ++k) {
-                if (!a[k].p) continue;
-                const uintptr_t a0 = (uintptr_t)a[k].p, a1 = a0 + a[k].bytes;
-                if (p0 < a1 && a0 < p1) {
-                    snprintf(msg, sizeof msg, "%s: %s must not alias %s", fn, outs[o].name, a[k].name);
-                    return wc_set_err(WC_EINVAL, msg);
-                }
-            }
-        }
-    }
-    return WC_OK;
-}
-
 int check_shape(const char* fn, int B, int R, int N) {
-    char msg[200];
-    if (B < 1) return snprintf(msg, sizeof msg, "%s: B < 1", fn), wc_set_err(WC_EINVAL, msg);
-    if (R < 1) return snprintf(msg, sizeof msg, "%s: R < 1", fn), wc_set_err(WC_EINVAL, msg);
-    if (N < 2) return snprintf(msg, sizeof msg, "%s: N < 2", fn), wc_set_err(WC_EINVAL, msg);
-    if (N > kMaxN) {
-        snprintf(msg, sizeof msg, "%s: N = %d > 96 (one matrix per workgroup, in LDS)", fn, N);
-        return wc_set_err(WC_EUNSUPPORTED, msg);
-    }
+    if (B < 1) return wc_fail(WC_EINVAL, "%s: B < 1", fn);
+    if (R < 1) return wc_fail(WC_EINVAL, "%s: R < 1", fn);
+    if (N < 2) return wc_fail(WC_EINVAL, "%s: N < 2", fn);
+    if (N > kMaxN) return wc_fail(WC_EUNSUPPORTED, "%s: N = %d > 96 (one matrix per workgroup, in LDS)", fn, N);
     return WC_OK;
 }
 
@@ -333,19 +290,16 @@ int wc_graph_louvain(int B, int R, int N, const double* obj, const double* norm,
     wc_clear_err();
     const char* fn = "wc_graph_louvain";
     if (int rc = check_shape(fn, B, R, N)) return rc;
-    if ((int64_t)B * R > INT32_MAX) return wc_set_err(WC_EINVAL, "wc_graph_louvain: 2^31 workgroups or more (B times R)");
+    if ((int64_t)B * R > INT32_MAX) return wc_fail(WC_EINVAL, "wc_graph_louvain: 2^31 workgroups or more (B times R)");
     if (!obj || !norm || !seeds || !ci || !q)
-        return wc_set_err(WC_EINVAL, "wc_graph_louvain: obj, norm, seeds, ci or q is NULL");
+        return wc_fail(WC_EINVAL, "wc_graph_louvain: obj, norm, seeds, ci or q is NULL");
     const size_t b = B, r = R, n = N;
-    const Span ins[4] = {{"obj", obj, b * n * n * 8, 8}, {"norm", norm, b * 8, 8}, {"ci0", ci0, b * n * 4, 4},
+    const WcSpan ins[4] = {{"obj", obj, b * n * n * 8, 8}, {"norm", norm, b * 8, 8}, {"ci0", ci0, b * n * 4, 4},
                          {"seeds", seeds, r * 8, 8}};
-    const Span outs[3] = {{"ci", ci, b * r * n * 4, 4}, {"q", q, b * r * 8, 8}, {"info", info, b * r * 2 * 4, 4}};
-    if (int rc = check_spans(fn, ins, 4, outs, 3)) return rc;
+    const WcSpan outs[3] = {{"ci", ci, b * r * n * 4, 4}, {"q", q, b * r * 8, 8}, {"info", info, b * r * 2 * 4, 4}};
+    if (int rc = wc_check_spans(fn, ins, 4, outs, 3)) return rc;
     const size_t lds = louvain_lds_bytes(N);
-    if (lds > 65536) {
-        hipError_t e = hipFuncSetAttribute((const void*)louvain_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return wc_set_err(WC_EHIP, hipGetErrorString(e));
-    }
+    if (int rc = wc_raise_lds(fn, louvain_kernel, lds)) return rc;
     hipLaunchKernelGGL(louvain_kernel, dim3((unsigned)(B * R)), dim3(kWave), lds, static_cast<hipStream_t>(stream), R, N,
                        obj, norm, ci0, seeds, ci, q, info);
     return wc_hip_check(fn);
@@ -355,11 +309,11 @@ int wc_graph_agreement(int B, int R, int N, const int32_t* ci, double* D, void* 
     wc_clear_err();
     const char* fn = "wc_graph_agreement";
     if (int rc = check_shape(fn, B, R, N)) return rc;
-    if (!ci || !D) return wc_set_err(WC_EINVAL, "wc_graph_agreement: ci or D is NULL");
+    if (!ci || !D) return wc_fail(WC_EINVAL, "wc_graph_agreement: ci or D is NULL");
     const size_t b = B, r = R, n = N;
-    const Span ins[1] = {{"ci", ci, b * r * n * 4, 4}};
-    const Span outs[1] = {{"D", D, b * n * n * 8, 8}};
-    if (int rc = check_spans(fn, ins, 1, outs, 1)) return rc;
+    const WcSpan ins[1] = {{"ci", ci, b * r * n * 4, 4}};
+    const WcSpan outs[1] = {{"D", D, b * n * n * 8, 8}};
+    if (int rc = wc_check_spans(fn, ins, 1, outs, 1)) return rc;
     hipLaunchKernelGGL(agreement_kernel, dim3(B), dim3(kAgThreads), 0, static_cast<hipStream_t>(stream), R, N, ci, D);
     return wc_hip_check(fn);
 }

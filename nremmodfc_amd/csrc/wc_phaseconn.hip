@@ -281,44 +281,32 @@ size_t wc_phase_conn_workspace_size(int B, int N, int64_t M, int measures) {
 int wc_phase_conn(int B, int N, int64_t M, const double* phasor, const double* amp, int measures, double* out,
                   void* workspace, size_t ws_bytes, void* stream) {
     wc_clear_err();
-    char msg[200];
-    if (B < 1) return wc_set_err(WC_EINVAL, "wc_phase_conn: B < 1");
-    if (N < 1) return wc_set_err(WC_EINVAL, "wc_phase_conn: N < 1");
-    if (M < 2) return wc_set_err(WC_EINVAL, "wc_phase_conn: M < 2");
+    const char* fn = "wc_phase_conn";
+    if (B < 1) return wc_fail(WC_EINVAL, "wc_phase_conn: B < 1");
+    if (N < 1) return wc_fail(WC_EINVAL, "wc_phase_conn: N < 1");
+    if (M < 2) return wc_fail(WC_EINVAL, "wc_phase_conn: M < 2");
     if (measures <= 0 || (measures & ~kAll))
-        return wc_set_err(WC_EINVAL, "wc_phase_conn: measures must be a non-empty set of WC_CONN_PLV .. WC_CONN_AEC_ORTH");
+        return wc_fail(WC_EINVAL, "wc_phase_conn: measures must be a non-empty set of WC_CONN_PLV .. WC_CONN_AEC_ORTH");
     const bool want_amp = measures & (WC_CONN_WPLI | WC_CONN_AEC_ORTH);
-    if (!phasor || !out) return wc_set_err(WC_EINVAL, "wc_phase_conn: phasor or out is NULL");
+    if (!phasor || !out) return wc_fail(WC_EINVAL, "wc_phase_conn: phasor or out is NULL");
     if (want_amp && !amp)
-        return wc_set_err(WC_EINVAL, "wc_phase_conn: amp is NULL (WC_CONN_WPLI and WC_CONN_AEC_ORTH need the envelopes)");
-    if (N > kMaxN) {
-        snprintf(msg, sizeof msg, "wc_phase_conn: N = %d > 1024 columns per simulation", N);
-        return wc_set_err(WC_EUNSUPPORTED, msg);
-    }
-    if (M > kMaxM) {
-        snprintf(msg, sizeof msg, "wc_phase_conn: M = %lld > 524288 (the Hilbert range)", (long long)M);
-        return wc_set_err(WC_EUNSUPPORTED, msg);
-    }
+        return wc_fail(WC_EINVAL, "wc_phase_conn: amp is NULL (WC_CONN_WPLI and WC_CONN_AEC_ORTH need the envelopes)");
+    if (N > kMaxN) return wc_fail(WC_EUNSUPPORTED, "wc_phase_conn: N = %d > 1024 columns per simulation", N);
+    if (M > kMaxM) return wc_fail(WC_EUNSUPPORTED, "wc_phase_conn: M = %lld > 524288 (the Hilbert range)", (long long)M);
     PcPlan p;
     if (!pc_plan(B, N, M, measures, p))
-        return wc_set_err(WC_EINVAL, "wc_phase_conn: 2^31 workgroups or more (B times the tile pairs)");
-    {
-        // B N <= 32 B nt <= 32 B ntp < 2^36 and M < 2^20: the phasors are below 2^60 bytes
-        const int nmeas = __builtin_popcount((unsigned)measures);
-        const size_t cells = (size_t)M * (size_t)B * (size_t)N;
-        const uintptr_t u0 = (uintptr_t)phasor, u1 = u0 + cells * 16, a0 = (uintptr_t)amp, a1 = a0 + cells * 8,
-                        p0 = (uintptr_t)out, p1 = p0 + (size_t)nmeas * B * N * N * 8;
-        if ((p0 < u1 && u0 < p1) || (amp && p0 < a1 && a0 < p1))
-            return wc_set_err(WC_EINVAL, "wc_phase_conn: out must not alias phasor or amp");
-        if ((u0 & 7) || (a0 & 7) || (p0 & 7))
-            return wc_set_err(WC_EINVAL, "wc_phase_conn: phasor, amp and out must be 8-byte aligned");
-    }
-    const size_t need = p.part + p.col;
-    if (!workspace || ws_bytes < need) {
-        snprintf(msg, sizeof msg, "wc_phase_conn: workspace < %zu bytes (wc_phase_conn_workspace_size)", need);
-        return wc_set_err(WC_EWORKSPACE, msg);
-    }
-    if ((uintptr_t)workspace & 15) return wc_set_err(WC_EINVAL, "wc_phase_conn: workspace must be 16-byte aligned");
+        return wc_fail(WC_EINVAL, "wc_phase_conn: 2^31 workgroups or more (B times the tile pairs)");
+    // B N <= 32 B nt <= 32 B ntp < 2^36 and M < 2^20: the phasors are below 2^60 bytes
+    const size_t nmeas = (size_t)__builtin_popcount((unsigned)measures);
+    const size_t cells = (size_t)M * (size_t)B * (size_t)N;
+    const WcSpan ins[2] = {{"phasor", phasor, cells * 16, 8}, {"amp", amp, cells * 8, 8}};
+    const WcSpan outs[2] = {{"out", out, nmeas * B * N * N * 8, 8}, {"workspace", workspace, ws_bytes, 16}};
+    // aliasing is refused before alignment here, and the workspace's alignment after its size
+    if (int rc = wc_check_alias(fn, outs, 1, ins, 2)) return rc;
+    if (int rc = wc_check_align(fn, ins, 2)) return rc;
+    if (int rc = wc_check_align(fn, outs, 1)) return rc;
+    if (int rc = wc_check_workspace(fn, "wc_phase_conn_workspace_size", workspace, ws_bytes, p.part + p.col)) return rc;
+    if (int rc = wc_check_align(fn, outs + 1, 1)) return rc;
 
     hipStream_t st = static_cast<hipStream_t>(stream);
     double* part = static_cast<double*>(workspace);

@@ -100,14 +100,14 @@ __global__ void __launch_bounds__(kThreads) sp_kernel(const SpArgs a) {
 }
 
 template <int MODE>
-hipError_t sp_dispatch(int logL, const SpArgs& a, int pairs, hipStream_t st) {
+int sp_dispatch(int logL, const SpArgs& a, int pairs, hipStream_t st) {
     return bs_dispatch(logL, [&](auto I) {
         constexpr int LOGN = decltype(I)::value;
-        return bs_launch<LOGN>(sp_kernel<LOGN, MODE>, bs_grid(LOGN, a.C, pairs), st, a);
+        return bs_launch<LOGN>("wc_spectrogram", sp_kernel<LOGN, MODE>, bs_grid(LOGN, a.C, pairs), st, a);
     });
 }
 
-hipError_t sp_dispatch_mode(int mode, int logL, const SpArgs& a, int pairs, hipStream_t st) {
+int sp_dispatch_mode(int mode, int logL, const SpArgs& a, int pairs, hipStream_t st) {
     switch (mode) {
         case WC_SPEC_PSD: return sp_dispatch<WC_SPEC_PSD>(logL, a, pairs, st);
         case WC_SPEC_COMPLEX: return sp_dispatch<WC_SPEC_COMPLEX>(logL, a, pairs, st);
@@ -125,13 +125,12 @@ size_t wc_spectrogram_workspace_size(int nperseg) {
 int wc_spectrogram(int64_t C, int64_t T, const double* x, int nperseg, int noverlap, const double* window,
                    int detrend, double scale, int mode, double* out, void* workspace, size_t ws_bytes, void* stream) {
     wc_clear_err();
-    char msg[200];
+    const char* fn = "wc_spectrogram";
     const int n = nperseg;
-    if (C > kMaxC) return wc_set_err(WC_EINVAL, "wc_spectrogram: C > 2^24");
-    if (int rc = bs_check_args("wc_spectrogram", "out", C, T, x, n, noverlap, window, detrend, scale, out, workspace))
-        return rc;
+    if (C > kMaxC) return wc_fail(WC_EINVAL, "wc_spectrogram: C > 2^24");
+    if (int rc = bs_check_args(fn, "out", C, T, x, n, noverlap, window, detrend, scale, out, workspace)) return rc;
     if (mode < WC_SPEC_PSD || mode > WC_SPEC_ANGLE)
-        return wc_set_err(WC_EINVAL, "wc_spectrogram: unknown mode (WC_SPEC_PSD .. WC_SPEC_ANGLE)");
+        return wc_fail(WC_EINVAL, "wc_spectrogram: unknown mode (WC_SPEC_PSD .. WC_SPEC_ANGLE)");
     const int F = n / 2 + 1;
     const int nseg = (int)((T - n) / (n - noverlap) + 1);
     {
@@ -140,29 +139,22 @@ int wc_spectrogram(int64_t C, int64_t T, const double* x, int nperseg, int nover
         const unsigned __int128 xb = (unsigned __int128)T * (unsigned __int128)C * 8;
         const unsigned __int128 ob =
             (unsigned __int128)nseg * (unsigned)F * (unsigned __int128)C * (mode == WC_SPEC_COMPLEX ? 16 : 8);
-        if (xb >= lim) return wc_set_err(WC_EINVAL, "wc_spectrogram: x of 2^62 bytes or more");
-        if (ob >= lim) return wc_set_err(WC_EINVAL, "wc_spectrogram: an output of 2^62 bytes or more");
-        const uintptr_t x0 = (uintptr_t)x, x1 = x0 + (size_t)xb, p0 = (uintptr_t)out, p1 = p0 + (size_t)ob;
-        if (p0 < x1 && x0 < p1) return wc_set_err(WC_EINVAL, "wc_spectrogram: out must not alias x");
+        if (xb >= lim) return wc_fail(WC_EINVAL, "wc_spectrogram: x of 2^62 bytes or more");
+        if (ob >= lim) return wc_fail(WC_EINVAL, "wc_spectrogram: an output of 2^62 bytes or more");
+        const WcSpan in = {"x", x, (size_t)xb, 8}, o = {"out", out, (size_t)ob, 8};
+        if (int rc = wc_check_alias(fn, &o, 1, &in, 1)) return rc;
     }
     const BsTables tab = bs_layout(n, workspace);
-    if (!workspace || ws_bytes < tab.bytes) {
-        snprintf(msg, sizeof msg, "wc_spectrogram: workspace < %zu bytes (wc_spectrogram_workspace_size)", tab.bytes);
-        return wc_set_err(WC_EWORKSPACE, msg);
-    }
+    if (int rc = wc_check_workspace(fn, "wc_spectrogram_workspace_size", workspace, ws_bytes, tab.bytes)) return rc;
 
     hipStream_t st = static_cast<hipStream_t>(stream);
-    hipError_t e = bs_fill_tables(tab, n, st);
+    int rc = bs_fill_tables(fn, tab, n, st);
     const double mul = mode == WC_SPEC_PSD ? scale : sqrt(scale);
     SpArgs a{C, n, n - noverlap, nseg, 0, detrend, mul, x, window, tab.T, tab.w, tab.Bf, out};
-    for (int64_t s0 = 0; s0 < nseg && e == hipSuccess; s0 += 2 * (int64_t)kMaxPairs) {
+    for (int64_t s0 = 0; s0 < nseg && rc == WC_OK; s0 += 2 * (int64_t)kMaxPairs) {
         const int segs = (int)std::min<int64_t>(2 * (int64_t)kMaxPairs, nseg - s0);
         a.s0 = (int)s0;
-        e = sp_dispatch_mode(mode, tab.logL, a, (segs + 1) / 2, st);
+        rc = sp_dispatch_mode(mode, tab.logL, a, (segs + 1) / 2, st);
     }
-    if (e != hipSuccess) {
-        snprintf(wc_errbuf(), 512, "wc_spectrogram: %s", hipGetErrorString(e));
-        return WC_EHIP;
-    }
-    return wc_hip_check("wc_spectrogram");
+    return rc ? rc : wc_hip_check(fn);
 }

@@ -144,20 +144,14 @@ size_t wc_welch_psd_workspace_size(int64_t C, int64_t T, int nperseg, int noverl
 int wc_welch_psd(int64_t C, int64_t T, const double* x, int nperseg, int noverlap, const double* window, int detrend,
                  double scale, double* psd, void* workspace, size_t ws_bytes, void* stream) {
     wc_clear_err();
-    char msg[200];
+    const char* fn = "wc_welch_psd";
     const int n = nperseg;
-    if (int rc = bs_check_args("wc_welch_psd", "psd", C, T, x, n, noverlap, window, detrend, scale, psd, workspace))
-        return rc;
+    if (int rc = bs_check_args(fn, "psd", C, T, x, n, noverlap, window, detrend, scale, psd, workspace)) return rc;
     const WpPlan p = wp_plan(T, n, noverlap, workspace);
-    {
-        const uintptr_t x0 = (uintptr_t)x, x1 = x0 + (size_t)T * C * 8, p0 = (uintptr_t)psd, p1 = p0 + (size_t)p.F * C * 8;
-        if (p0 < x1 && x0 < p1) return wc_set_err(WC_EINVAL, "wc_welch_psd: psd must not alias x");
-    }
-    const size_t need = p.tab.bytes + p.per_col;
-    if (!workspace || ws_bytes < need) {
-        snprintf(msg, sizeof msg, "wc_welch_psd: workspace < %zu bytes (wc_welch_psd_workspace_size)", need);
-        return wc_set_err(WC_EWORKSPACE, msg);
-    }
+    const WcSpan in = {"x", x, (size_t)T * C * 8, 8}, o = {"psd", psd, (size_t)p.F * C * 8, 8};
+    if (int rc = wc_check_alias(fn, &o, 1, &in, 1)) return rc;
+    if (int rc = wc_check_workspace(fn, "wc_welch_psd_workspace_size", workspace, ws_bytes, p.tab.bytes + p.per_col))
+        return rc;
 
     hipStream_t st = static_cast<hipStream_t>(stream);
     double* partial = reinterpret_cast<double*>(p.tab.Bf + ((size_t)1 << p.tab.logL));
@@ -165,25 +159,21 @@ int wc_welch_psd(int64_t C, int64_t T, const double* x, int nperseg, int noverla
     const int64_t tcmax =
         (int64_t)std::min<size_t>((ws_bytes - p.tab.bytes) / p.per_col, (size_t)std::min<int64_t>(C, 1 << 20));
 
-    hipError_t e = bs_fill_tables(p.tab, n, st);
+    int rc = bs_fill_tables(fn, p.tab, n, st);
     WpArgs a{C, 0, 1, n, n - noverlap, p.nseg, p.sb, detrend, x, window, p.tab.T, p.tab.w, p.tab.Bf, partial};
     const double mult = scale / (double)p.nseg;
-    for (int64_t c0 = 0; c0 < C && e == hipSuccess; c0 += tcmax) {
+    for (int64_t c0 = 0; c0 < C && rc == WC_OK; c0 += tcmax) {
         a.c0 = c0;
         a.tc = (int)std::min<int64_t>(tcmax, C - c0);
-        e = bs_dispatch(p.tab.logL, [&](auto I) {
+        rc = bs_dispatch(p.tab.logL, [&](auto I) {
             constexpr int LOGN = decltype(I)::value;
-            return bs_launch<LOGN>(wp_kernel<LOGN>, bs_grid(LOGN, a.tc, p.nb), st, a);
+            return bs_launch<LOGN>(fn, wp_kernel<LOGN>, bs_grid(LOGN, a.tc, p.nb), st, a);
         });
         const int64_t tot = (int64_t)p.F * a.tc;
-        if (e == hipSuccess)
+        if (rc == WC_OK)
             hipLaunchKernelGGL(wp_finish_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, C, c0, a.tc, n,
                                p.nb, mult, partial, psd);
     }
-    if (e != hipSuccess) {
-        snprintf(wc_errbuf(), 512, "wc_welch_psd: %s", hipGetErrorString(e));
-        return WC_EHIP;
-    }
-    return wc_hip_check("wc_welch_psd");
+    return rc ? rc : wc_hip_check(fn);
 }
 
