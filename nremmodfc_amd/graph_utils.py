@@ -100,12 +100,27 @@ def _matrices(name, W, nonnegative):
     return a
 
 
-def _device(a, names, **kw):
+def _on_device(fn, *arrays, **kw):
+    """sigchain's `fn` on device copies of the numpy arrays among its arguments (anything else goes as it
+    is), its tensors back as numpy arrays.  torch and sigchain are imported here, on first use."""
     import torch
 
     from . import sigchain
-    got = sigchain.graph_measures(torch.from_numpy(a).cuda(), names, **kw)
-    return [got[m].cpu().numpy() for m in names]
+
+    def up(v):
+        return torch.from_numpy(v).cuda() if isinstance(v, np.ndarray) else v
+
+    def down(v):
+        if isinstance(v, dict):
+            return {k: down(x) for k, x in v.items()}
+        return tuple(down(x) for x in v) if isinstance(v, tuple) else v.cpu().numpy()
+
+    return down(getattr(sigchain, fn)(*map(up, arrays), **{k: up(v) for k, v in kw.items()}))
+
+
+def _device(a, names, **kw):
+    got = _on_device("graph_measures", a, names, **kw)
+    return [got[m] for m in names]
 
 
 def distance_wei(G):
@@ -169,23 +184,17 @@ def degrees_und(CIJ):
 
 # ---- node measures on the device (sigchain.graph_betweenness, sigchain.graph_module_measures) ----
 
-def _betweenness(a):
-    import torch
-
-    from . import sigchain
-    return sigchain.graph_betweenness(torch.from_numpy(a).cuda(), lengths=True).cpu().numpy()
-
-
 def betweenness_wei(G):
     """Node betweenness centrality over the connection lengths G (graph_utils.py:1983-2052): ordered
     pairs, so an undirected graph has twice the textbook value."""
-    return _betweenness(_matrices("betweenness_wei", G, True))
+    return _on_device("graph_betweenness", _matrices("betweenness_wei", G, True), lengths=True)
 
 
 def betweenness_bin(G):
     """Node betweenness centrality of a binary graph (graph_utils.py:1929-1980): the same kernel on
     the lengths (G != 0)."""
-    return _betweenness((_matrices("betweenness_bin", G, False) != 0).astype(np.float64))
+    return _on_device("graph_betweenness", (_matrices("betweenness_bin", G, False) != 0).astype(np.float64),
+                      lengths=True)
 
 
 def _labels(name, ci, a):
@@ -202,12 +211,7 @@ def _labels(name, ci, a):
 
 
 def _modules(a, lab, K, name, **kw):
-    import torch
-
-    from . import sigchain
-    got = sigchain.graph_module_measures(torch.from_numpy(a).cuda(), torch.from_numpy(lab).cuda(), (name,),
-                                         n_modules=K, **kw)
-    return got[name].cpu().numpy()
+    return _on_device("graph_module_measures", a, lab, (name,), n_modules=K, **kw)[name]
 
 
 def participation_coef(W, ci, degree="undirected"):
@@ -255,11 +259,6 @@ def _louvain_args(name, W, ci, B):
     return a, lab, obj
 
 
-def _to_device(x):
-    import torch
-    return torch.from_numpy(x).cuda() if isinstance(x, np.ndarray) else x
-
-
 def community_louvain(W, gamma=1, ci=None, B="modularity", seed=None):
     """(ci, q): Louvain community structure of W and the objective reached (graph_utils.py:958-1122);
     labels from 1.  B 'modularity', 'potts' or an objective matrix (symmetrised with a warning where
@@ -274,14 +273,11 @@ def community_louvain(W, gamma=1, ci=None, B="modularity", seed=None):
     negative weights first), modularity_louvain_und_sign, consensus_und, modularity_und's spectral
     search, N > 96."""
     import os
-
-    from . import sigchain
     a, lab, obj = _louvain_args("community_louvain", W, ci, B)
     if seed is None:
         seed = int.from_bytes(os.urandom(8), "little")
-    part, q = sigchain.graph_louvain(_to_device(a), seeds=int(seed), gamma=float(gamma),
-                                     ci=None if lab is None else _to_device(lab), objective=_to_device(obj))
-    part, q = part.cpu().numpy().astype(np.int64) + 1, q.cpu().numpy()
+    part, q = _on_device("graph_louvain", a, seeds=int(seed), gamma=float(gamma), ci=lab, objective=obj)
+    part = part.astype(np.int64) + 1
     return (part, float(q)) if a.ndim == 2 else (part, q)
 
 
@@ -289,9 +285,6 @@ def agreement(ci, buffsz=1000):
     """Agreement matrix D of the partitions ci [N, M], one per column, the reference's orientation
     (graph_utils.py:890-932): D[i, j] partitions put i and j together; 0 on the diagonal.  A
     [B, N, M] stack gives [B, N, N].  buffsz is accepted and ignored."""
-    import torch
-
-    from . import sigchain
     c = np.asarray(ci)
     if c.ndim not in (2, 3) or c.shape[-1] == 0:
         raise ValueError(f"agreement: ci needs [vertex x partition], or a [B, N, M] stack, got shape {c.shape}")
@@ -299,7 +292,7 @@ def agreement(ci, buffsz=1000):
         raise ValueError(f"agreement: N = {c.shape[-2]}, the device kernels take 2 <= N <= {GRAPH_MAX_N}")
     lab = np.unique(c, return_inverse=True)[1].reshape(c.shape).astype(np.int32)   # any labels: equality is kept
     lab = np.ascontiguousarray(np.swapaxes(lab, -1, -2))
-    return sigchain.graph_agreement(torch.from_numpy(lab).cuda()).cpu().numpy()
+    return _on_device("graph_agreement", lab)
 
 
 def get_agreement_matrix(W, reps=100, tau=0.5, gamma=1, ci=None, B="modularity", seeds=None):
@@ -308,11 +301,8 @@ def get_agreement_matrix(W, reps=100, tau=0.5, gamma=1, ci=None, B="modularity",
     seeds given (it reads seed_vector before assigning it); this accepts a sequence of length reps.
     W is an N x N matrix or a [B, N, N] stack.  The visiting order is the engine's: see
     community_louvain."""
-    from . import sigchain
     a, lab, obj = _louvain_args("get_agreement_matrix", W, ci, B)
     if seeds is not None and (np.ndim(seeds) != 1 or len(seeds) != reps):
         raise ValueError("get_agreement_matrix: seeds must be an array of length equal to reps, or None")
-    D = sigchain.graph_consensus_matrix(_to_device(a), reps=int(reps), tau=float(tau), gamma=float(gamma),
-                                        ci=None if lab is None else _to_device(lab), objective=_to_device(obj),
-                                        seeds=None if seeds is None else [int(v) for v in seeds])
-    return D.cpu().numpy()
+    return _on_device("graph_consensus_matrix", a, reps=int(reps), tau=float(tau), gamma=float(gamma), ci=lab,
+                      objective=obj, seeds=None if seeds is None else [int(v) for v in seeds])

@@ -20,12 +20,15 @@ import warnings
 import numpy as np
 import torch
 
-from . import _lib
+from . import _args, _lib
 from .filters import bold_band, lfilter_zi
 
 NEQ = 2000          # wc:145
 WELCH_NPERSEG = 4000  # whole_sweep_both.py:90
 WELCH_HOP = WELCH_NPERSEG // 2
+
+
+_FROM_2D = range(2, 65)   # [T][C], [T][B][N] and beyond: the columns are whatever follows the time axis
 
 
 def _ptr_at(t, offset_elems=0):
@@ -83,6 +86,10 @@ class BoldStream:
         return out
 
 
+HILBERT_DIRECT_MAX_M = 8192       # wc_hilbert_phase: M * 8 bytes of LDS in a 64 KB launch
+HILBERT_LONG_WS_CAP = 1 << 30     # wc_hilbert_phase_long: workspace ceiling (column tiles beyond it)
+
+
 def hilbert_phase(x):
     """Unit phasors of hilbert(x, axis=0) for x [M][C] fp64 -> [M][C][2].
 
@@ -93,15 +100,19 @@ def hilbert_phase(x):
     M, C = x.shape
     ph = torch.empty((M, C, 2), dtype=torch.float64, device=x.device)
     if M <= HILBERT_DIRECT_MAX_M:
-        ws = torch.empty(M, dtype=torch.float64, device=x.device)
-        _lib.check(_lib.lib().wc_hilbert_phase(C, M, _lib.ptr(x.contiguous()), _lib.ptr(ph), _lib.ptr(ws),
-                                               ws.numel() * 8, _lib.stream_handle()), "wc_hilbert_phase")
+        ws = _args.workspace(M * 8, x.device)
+        _lib.check(_lib.lib().wc_hilbert_phase(C, M, _lib.ptr(x.contiguous()), _lib.ptr(ph), _lib.ptr(ws), M * 8,
+                                               _lib.stream_handle()), "wc_hilbert_phase")
         return ph
     return hilbert_phase_long(x, ph)
 
 
-HILBERT_DIRECT_MAX_M = 8192       # wc_hilbert_phase: M * 8 bytes of LDS in a 64 KB launch
-HILBERT_LONG_WS_CAP = 1 << 30     # wc_hilbert_phase_long: workspace ceiling (column tiles beyond it)
+def _hilbert_long_ws(need, C, M, ws_bytes):
+    """ws_bytes of the Bluestein path: the caller's, or by default what all C columns want."""
+    if ws_bytes is not None:
+        return ws_bytes
+    fft_len = max(1 << 15, 1 << (2 * M - 2).bit_length())  # max(2^15, nextpow2(2 M - 1))
+    return _args.ws_default(need, need + (C - 1) * 32 * fft_len, HILBERT_LONG_WS_CAP)
 
 
 def hilbert_phase_long(x, out=None, ws_bytes=None):
@@ -114,11 +125,9 @@ def hilbert_phase_long(x, out=None, ws_bytes=None):
     need = L.wc_hilbert_long_workspace_size(C, M)
     if need == 0:
         raise _lib.WCSDEError(f"hilbert_phase: M = {M} outside 2 .. 524288 (or no columns)")
-    if ws_bytes is None:
-        fft_len = max(1 << 15, 1 << (2 * M - 2).bit_length())  # max(2^15, nextpow2(2 M - 1))
-        ws_bytes = max(need, min(need + (C - 1) * 32 * fft_len, HILBERT_LONG_WS_CAP))
+    ws_bytes = _hilbert_long_ws(need, C, M, ws_bytes)
     ph = torch.empty((M, C, 2), dtype=torch.float64, device=x.device) if out is None else out
-    ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.float64, device=x.device)
+    ws = _args.workspace(ws_bytes, x.device)
     _lib.check(L.wc_hilbert_phase_long(C, M, _lib.ptr(x.contiguous()), _lib.ptr(ph), _lib.ptr(ws), ws_bytes,
                                        _lib.stream_handle()), "wc_hilbert_phase_long")
     return ph
@@ -137,14 +146,11 @@ def hilbert_envelope(x, method=0, ws_bytes=None):
     if need == 0:
         raise _lib.WCSDEError(f"hilbert_envelope: M = {M} outside 2 .. 524288 (8192 for method 1), no columns "
                               f"or method = {method} not 0, 1, 2")
-    if need == M * 8:  # the direct method: q[0..M), nothing to gain from more
-        ws_bytes = need
-    elif ws_bytes is None:
-        fft_len = max(1 << 15, 1 << (2 * M - 2).bit_length())  # max(2^15, nextpow2(2 M - 1))
-        ws_bytes = max(need, min(need + (C - 1) * 32 * fft_len, HILBERT_LONG_WS_CAP))
+    # the direct method: q[0..M), nothing to gain from more
+    ws_bytes = need if need == M * 8 else _hilbert_long_ws(need, C, M, ws_bytes)
     x = x.contiguous()
     env = torch.empty((M, C), dtype=torch.float64, device=x.device)
-    ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.float64, device=x.device)
+    ws = _args.workspace(ws_bytes, x.device)
     _lib.check(L.wc_hilbert_envelope(C, M, _lib.ptr(x), _lib.ptr(env), method, _lib.ptr(ws), ws_bytes,
                                      _lib.stream_handle()), "wc_hilbert_envelope")
     return env
@@ -158,8 +164,7 @@ def filtfilt(b, a, x):
     a = np.asarray(a, dtype=np.float64)
     if b.ndim != 1 or b.shape != a.shape:
         raise ValueError("filtfilt: b and a must be 1-D arrays of the same length")
-    if x.dtype != torch.float64 or x.dim() < 2:
-        raise TypeError("filtfilt: x must be a [T][C] or [T][B][N] fp64 device tensor")
+    _args.tensor("filtfilt", "x must be a [T][C] or [T][B][N] fp64 device tensor", x, torch.float64, _FROM_2D)
     zi = lfilter_zi(b, a)
     x = x.contiguous()
     y = torch.empty_like(x)
@@ -218,7 +223,7 @@ def fc_metrics(bold=None, B=None, N=None, empfc=None, fc_in=None, kuramoto=True,
     fc = torch.empty((B, N, N), dtype=torch.float64, device=dev) if want_fc else None
     ph = hilbert_phase(bold) if kuramoto else None
     nws = L.wc_fc_metrics_workspace_size(B, N, M, K, int(want_fc))  # 0 for N <= 96
-    ws = torch.empty(nws // 8 + 1, dtype=torch.float64, device=dev) if nws else None
+    ws = _args.workspace(nws, dev) if nws else None
     rc = L.wc_fc_metrics(B, N, M, _lib.ptr(bold) if bold is not None else None, _lib.ptr(fc_in), _lib.ptr(emp), K,
                          float(data_range), _lib.ptr(ph), _lib.ptr(fc), _lib.ptr(metrics), _lib.ptr(extra),
                          _lib.ptr(ws), nws, _lib.stream_handle())
@@ -235,6 +240,11 @@ def kuramoto(x, B=1, N=None):
     out = torch.empty((B, 2), dtype=torch.float64, device=x.device)
     _lib.check(_lib.lib().wc_kuramoto(B, N, M, _lib.ptr(ph), _lib.ptr(out), _lib.stream_handle()), "wc_kuramoto")
     return out
+
+
+HMA_JACOBI_MAX_N = 96   # wc_hma: F and V (2 N^2 fp64) in one workgroup's LDS
+HMA_MODES_MAX_N = 4096  # wc_hma_modes: 2 N fp64 + 6 N int32 label arrays (40 N B) in 160 KB of LDS
+HMA_EIGH_BATCH = 64     # N > 96: matrices per eigensolver call (bounds the V buffers)
 
 
 def hma(fc, want_clus_num=False):
@@ -257,11 +267,12 @@ def hma(fc, want_clus_num=False):
     out = {k: torch.empty(s, dtype=torch.float64, device=dev)
            for k, s in (("hin", (B,)), ("hse", (B,)), ("hin_node", (B, N)), ("hse_node", (B, N)), ("sv", (B, N)))}
     cn = torch.empty((B, N - 1), dtype=torch.int32, device=dev) if want_clus_num else None
+    res = dict(out, clus_num=cn) if want_clus_num else out
     if N <= HMA_JACOBI_MAX_N:
         rc = L.wc_hma(B, N, _lib.ptr(fc), _lib.ptr(out["hin"]), _lib.ptr(out["hse"]), _lib.ptr(out["hin_node"]),
                       _lib.ptr(out["hse_node"]), _lib.ptr(cn), _lib.ptr(out["sv"]), _lib.stream_handle())
         _lib.check(rc, "wc_hma")
-        return _with_cn(out, cn)
+        return res
     if N > HMA_MODES_MAX_N:  # fail before the eigensolver, not in wc_hma_modes
         raise _lib.WCSDEError(f"hma: N = {N} > {HMA_MODES_MAX_N} (wc_hma_modes keeps 40 B of labels per node in LDS)")
     # N > 96: F and V no longer fit one workgroup's LDS.  The eigensystem of the symmetrised
@@ -285,18 +296,7 @@ def hma(fc, want_clus_num=False):
                             _lib.stream_handle())
         _lib.check(rc, "wc_hma_modes")
         del lam, V, vt
-    return _with_cn(out, cn)
-
-
-HMA_JACOBI_MAX_N = 96   # wc_hma: F and V (2 N^2 fp64) in one workgroup's LDS
-HMA_MODES_MAX_N = 4096  # wc_hma_modes: 2 N fp64 + 6 N int32 label arrays (40 N B) in 160 KB of LDS
-HMA_EIGH_BATCH = 64     # N > 96: matrices per eigensolver call (bounds the V buffers)
-
-
-def _with_cn(out, cn):
-    if cn is not None:
-        out["clus_num"] = cn
-    return out
+    return res
 
 
 class WelchAccumulator:
@@ -353,26 +353,12 @@ def graph_measures(w, measures=GRAPH_MEASURES, lengths=False, include_infinite=T
     lengths=True goes with the path measures only: the others are defined on weights.
 
     Composes with fc_metrics(..., want_fc=True) and hma: both leave FC matrices of this layout."""
-    names = (measures,) if isinstance(measures, str) else tuple(measures)
-    for m in names:
-        if m not in GRAPH_MEASURES:
-            raise ValueError(f"graph_measures: unknown measure {m!r}, must be one of {list(GRAPH_MEASURES)}")
-    if not names:
-        raise ValueError(f"graph_measures: no measure asked for, choose from {list(GRAPH_MEASURES)}")
-    names = tuple(dict.fromkeys(names))
+    names = _args.names("graph_measures", measures, GRAPH_MEASURES)
     if lengths and any(m not in GRAPH_PATH_MEASURES for m in names):
         raise ValueError(f"graph_measures: lengths=True goes with the path measures {list(GRAPH_PATH_MEASURES)} "
                          "only, the others are defined on weights")
-    if not isinstance(w, torch.Tensor) or w.dtype != torch.float64 or w.dim() not in (2, 3) \
-            or w.shape[-1] != w.shape[-2]:
-        raise TypeError("graph_measures: w must be a [B][N][N] or [N][N] fp64 device tensor")
-    single = w.dim() == 2
-    B, N = (1 if single else w.shape[0]), w.shape[-1]
-    if N < 2 or N > GRAPH_MAX_N or B < 1:
-        raise ValueError(f"graph_measures: N = {N}, B = {B}: needs B >= 1 and 2 <= N <= {GRAPH_MAX_N} "
-                         "(one matrix per workgroup, in LDS)")
+    w, single, B, N = _graph_stack("graph_measures", w)
     L = _lib.lib()
-    w = w.contiguous()
     dev, st = w.device, _lib.stream_handle()
     want = set(names)
 
@@ -398,20 +384,16 @@ def graph_measures(w, measures=GRAPH_MEASURES, lengths=False, include_infinite=T
         _lib.check(L.wc_graph_clustering(B, N, _lib.ptr(w), _lib.ptr(clus), _lib.ptr(trans), _lib.ptr(stre),
                                          _lib.ptr(deg), st), "wc_graph_clustering")
         res.update(clustering=clus, transitivity=trans, strengths=stre, degrees=deg)
-    return {m: (res[m][0] if single else res[m]) for m in names}
+    return _args.unbatch(single, {m: res[m] for m in names})
 
 
 def _graph_stack(name, w):
     """(w contiguous, single, B, N) of a [B][N][N] or [N][N] fp64 tensor, refused before the device is touched."""
-    if not isinstance(w, torch.Tensor) or w.dtype != torch.float64 or w.dim() not in (2, 3) \
-            or w.shape[-1] != w.shape[-2]:
-        raise TypeError(f"{name}: w must be a [B][N][N] or [N][N] fp64 device tensor")
-    single = w.dim() == 2
-    B, N = (1 if single else w.shape[0]), w.shape[-1]
+    w, single, B, N = _args.stack(name, "w must be a [B][N][N] or [N][N] fp64 device tensor", w, square=True)
     if N < 2 or N > GRAPH_MAX_N or B < 1:
         raise ValueError(f"{name}: N = {N}, B = {B}: needs B >= 1 and 2 <= N <= {GRAPH_MAX_N} "
                          "(one matrix per workgroup, in LDS)")
-    return w.contiguous(), single, B, N
+    return w, single, B, N
 
 
 def graph_betweenness(w, lengths=False):
@@ -429,7 +411,7 @@ def graph_betweenness(w, lengths=False):
     bc = torch.empty((B, N), dtype=torch.float64, device=w.device)
     _lib.check(_lib.lib().wc_graph_betweenness(B, N, _lib.ptr(w), int(bool(lengths)), _lib.ptr(bc),
                                                _lib.stream_handle()), "wc_graph_betweenness")
-    return bc[0] if single else bc
+    return _args.unbatch(single, bc)
 
 
 GRAPH_MODULE_MEASURES = ("participation", "zscore", "modularity")
@@ -454,22 +436,14 @@ def graph_module_measures(w, ci, measures=GRAPH_MODULE_MEASURES, degree="undirec
     Newman for a directed matrix).  Negative weights are summed as they are.  Only the outputs asked
     for are allocated.  A matrix with a label out of range has NaN in every measure; no label is read
     back to the host."""
-    names = (measures,) if isinstance(measures, str) else tuple(measures)
-    for m in names:
-        if m not in GRAPH_MODULE_MEASURES:
-            raise ValueError(f"graph_module_measures: unknown measure {m!r}, must be one of "
-                             f"{list(GRAPH_MODULE_MEASURES)}")
-    if not names:
-        raise ValueError(f"graph_module_measures: no measure asked for, choose from {list(GRAPH_MODULE_MEASURES)}")
-    names = tuple(dict.fromkeys(names))
+    names = _args.names("graph_module_measures", measures, GRAPH_MODULE_MEASURES)
     if degree not in GRAPH_MODULE_DEGREES:
         raise ValueError(f"graph_module_measures: degree {degree!r}, must be one of {list(GRAPH_MODULE_DEGREES)}")
     if isinstance(zflag, bool) or not isinstance(zflag, int) or not 0 <= zflag <= 3:
         raise ValueError(f"graph_module_measures: zflag {zflag!r}, must be 0, 1, 2 or 3")
     w, single, B, N = _graph_stack("graph_module_measures", w)
-    if not isinstance(ci, torch.Tensor) or ci.dtype != torch.int32 or ci.dim() not in (1, 2) \
-            or ci.shape[-1] != N or (ci.dim() == 2 and ci.shape[0] != B):
-        raise TypeError(f"graph_module_measures: ci must be an int32 device tensor [N] or [B][N] with N = {N}, B = {B}")
+    _args.tensor("graph_module_measures", f"ci must be an int32 device tensor [N] or [B][N] with N = {N}, B = {B}", ci,
+                 torch.int32, shapes=((N,), (B, N)))
     K = N if n_modules is None else int(n_modules)
     if K < 1 or K > N:
         raise ValueError(f"graph_module_measures: n_modules = {n_modules}, must be in [1, N = {N}]")
@@ -484,7 +458,7 @@ def graph_module_measures(w, ci, measures=GRAPH_MODULE_MEASURES, degree="undirec
     _lib.check(_lib.lib().wc_graph_modules(B, N, K, _lib.ptr(w), _lib.ptr(ci), GRAPH_MODULE_DEGREES[degree], zflag,
                                            float(gamma), _lib.ptr(res["participation"]), _lib.ptr(res["zscore"]),
                                            _lib.ptr(res["modularity"]), _lib.stream_handle()), "wc_graph_modules")
-    return {m: (res[m][0] if single else res[m]) for m in names}
+    return _args.unbatch(single, {m: res[m] for m in names})
 
 
 GRAPH_LOUVAIN_OBJECTIVES = ("modularity", "potts")    # graph_louvain's built-in objectives; or a tensor
@@ -567,10 +541,9 @@ def graph_louvain(w, seeds=0, gamma=1.0, ci=None, objective="modularity", want_i
     w, single, B, N = _graph_stack(name, w)
     wb = w.reshape(B, N, N)
     dev = w.device
-    if custom and (objective.dtype != torch.float64 or objective.dim() not in (2, 3)
-                   or tuple(objective.shape[-2:]) != (N, N) or (objective.dim() == 3 and objective.shape[0] != B)
-                   or objective.device != dev):
-        raise TypeError(f"{name}: an objective tensor must be fp64 [N][N] or [B][N][N] on w's device, N = {N}, B = {B}")
+    if custom:
+        _args.tensor(name, f"an objective tensor must be fp64 [N][N] or [B][N][N] on w's device, N = {N}, B = {B}",
+                     objective, torch.float64, shapes=((N, N), (B, N, N)), device=dev)
     ci0 = None if ci is None else _louvain_labels(name, ci, B, N, dev)
     refuse = wb.min() < GRAPH_LOUVAIN_MIN_WEIGHT
     if not custom and objective == "potts":
@@ -601,12 +574,10 @@ def graph_louvain(w, seeds=0, gamma=1.0, ci=None, objective="modularity", want_i
     _lib.check(_lib.lib().wc_graph_louvain(B, R, N, _lib.ptr(obj), _lib.ptr(s), _lib.ptr(ci0), _lib.ptr(seeds_dev),
                                            _lib.ptr(out), _lib.ptr(q), _lib.ptr(info), _lib.stream_handle()),
                "wc_graph_louvain")
-    res = [out, q] + ([info] if want_info else [])
+    res = (out, q) + ((info,) if want_info else ())
     if scalar:
-        res = [t[:, 0] for t in res]
-    if single:
-        res = [t[0] for t in res]
-    return tuple(res)
+        res = tuple(t[:, 0] for t in res)
+    return _args.unbatch(single, res)
 
 
 def graph_agreement(ci):
@@ -614,17 +585,15 @@ def graph_agreement(ci):
     ci int32 device tensor [B][R][N] or [R][N] (graph_louvain's layout) -> D fp64 [B][N][N] or [N][N],
     the number of the R partitions in which i and j share a label, exact, 0 on the diagonal.  A
     negative label (a run that graph_louvain refused) makes its matrix's D NaN."""
-    if not isinstance(ci, torch.Tensor) or ci.dtype != torch.int32 or ci.dim() not in (2, 3):
-        raise TypeError("graph_agreement: ci must be an int32 device tensor [B][R][N] or [R][N]")
-    single = ci.dim() == 2
-    B, (R, N) = (1 if single else ci.shape[0]), ci.shape[-2:]
+    ci, single, B, N = _args.stack("graph_agreement", "ci must be an int32 device tensor [B][R][N] or [R][N]", ci,
+                                   torch.int32)
+    R = ci.shape[-2]
     if N < 2 or N > GRAPH_MAX_N or B < 1 or R < 1:
         raise ValueError(f"graph_agreement: N = {N}, R = {R}, B = {B}: needs B, R >= 1 and 2 <= N <= {GRAPH_MAX_N}")
-    ci = ci.contiguous()
     D = torch.empty((B, N, N), dtype=torch.float64, device=ci.device)
     _lib.check(_lib.lib().wc_graph_agreement(B, R, N, _lib.ptr(ci), _lib.ptr(D), _lib.stream_handle()),
                "wc_graph_agreement")
-    return D[0] if single else D
+    return _args.unbatch(single, D)
 
 
 def graph_consensus_matrix(w, reps=100, tau=0.5, gamma=1.0, ci=None, objective="modularity", seeds=None):
@@ -671,10 +640,8 @@ def fcd(x, window=None, step=None, method="corr", want_windows=False, trim=0, ws
     FCD_PHASE_MAX_M = 4096.  window and step have no meaning here and must be left None."""
     if method not in FCD_METHODS:
         raise ValueError(f"fcd: unknown method {method!r}, must be one of {list(FCD_METHODS)}")
-    if not isinstance(x, torch.Tensor) or x.dtype != torch.float64 or x.dim() not in (2, 3):
-        raise TypeError("fcd: x must be a [M][C] or [M][B][N] fp64 device tensor")
-    single = x.dim() == 2
-    M, B, N = x.shape[0], (1 if single else x.shape[1]), x.shape[-1]
+    x, single, B, N = _args.stack("fcd", "x must be a [M][C] or [M][B][N] fp64 device tensor", x, batch=1)
+    M = x.shape[0]
     if B < 1 or N > FCD_MAX_N:
         raise ValueError(f"fcd: N = {N}, B = {B}: needs B >= 1 and N <= {FCD_MAX_N} (one window's correlation "
                          "matrix, a tile's phasors per workgroup)")
@@ -689,9 +656,8 @@ def fcd(x, window=None, step=None, method="corr", want_windows=False, trim=0, ws
         if trim < 0 or N < 2 or M < 2 or Mt < 1 or Mt > FCD_PHASE_MAX_M:
             raise ValueError(f"fcd: method='phase' needs N >= 2, trim >= 0 and 1 <= M - 2 trim <= {FCD_PHASE_MAX_M} "
                              f"(N = {N}, M = {M}, trim = {trim})")
-        ph = hilbert_phase(x.reshape(M, B * N).contiguous())[trim:M - trim].view(Mt, B, N, 2)
-        out = fcd_from_phasors(ph)
-        return out[0] if single else out
+        ph = hilbert_phase(x.reshape(M, B * N))[trim:M - trim].view(Mt, B, N, 2)
+        return _args.unbatch(single, fcd_from_phasors(ph))
     if trim:
         raise ValueError("fcd: method='corr' takes no trim (it goes with method='phase')")
     if window is None:
@@ -705,35 +671,29 @@ def fcd(x, window=None, step=None, method="corr", want_windows=False, trim=0, ws
         raise ValueError(f"fcd: {nw} windows > {FCD_MAX_WINDOWS}: take a larger step")
     P = N * (N - 1) // 2
     need = L.wc_fcd_workspace_size(B, N, M, window, step)
-    nbytes = max(need, min((nw * P + nw) * 8 * B, FCD_WS_CAP)) if ws_bytes is None else int(ws_bytes)
-    x = x.contiguous()
+    nbytes = _args.ws_default(need, (nw * P + nw) * 8 * B, FCD_WS_CAP) if ws_bytes is None else int(ws_bytes)
     out = torch.empty((B, nw, nw), dtype=torch.float64, device=x.device)
     pats = torch.empty((B, nw, P), dtype=torch.float64, device=x.device) if want_windows else None
-    ws = torch.empty((max(nbytes, 8) + 7) // 8, dtype=torch.float64, device=x.device)
+    ws = _args.workspace(nbytes, x.device)
     _lib.check(L.wc_fcd(B, N, M, _lib.ptr(x), window, step, _lib.ptr(out), _lib.ptr(pats), _lib.ptr(ws), nbytes,
                         _lib.stream_handle()), "wc_fcd")
-    if single:
-        out, pats = out[0], (pats[0] if want_windows else None)
-    return (out, pats) if want_windows else out
+    return _args.unbatch(single, (out, pats) if want_windows else out)
 
 
 def fcd_from_phasors(phasor):
     """The phase-coherence FCD (wc_fcd_phase) of unit phasors the caller already holds: phasor
     [M][C][2] or [M][B][N][2] fp64 (hilbert_phase's output, trimmed as wanted) -> [M][M] or [B][M][M];
     see fcd(method="phase").  2 <= N <= 96, M <= FCD_PHASE_MAX_M = 4096."""
-    if not isinstance(phasor, torch.Tensor) or phasor.dtype != torch.float64 or phasor.dim() not in (3, 4) \
-            or phasor.shape[-1] != 2:
-        raise TypeError("fcd_from_phasors: phasor must be a [M][C][2] or [M][B][N][2] fp64 device tensor")
-    single = phasor.dim() == 3
-    M, B, N = phasor.shape[0], (1 if single else phasor.shape[1]), phasor.shape[-2]
+    phasor, single, B, N = _args.stack("fcd_from_phasors", "phasor must be a [M][C][2] or [M][B][N][2] fp64 device "
+                                       "tensor", phasor, ndim=4, batch=1, last=2)
+    M = phasor.shape[0]
     if B < 1 or N < 2 or N > FCD_MAX_N or M < 1 or M > FCD_PHASE_MAX_M:
         raise ValueError(f"fcd_from_phasors: N = {N}, B = {B}, M = {M}: needs B >= 1, 2 <= N <= {FCD_MAX_N} and "
                          f"1 <= M <= {FCD_PHASE_MAX_M}")
-    phasor = phasor.contiguous()
     out = torch.empty((B, M, M), dtype=torch.float64, device=phasor.device)
     _lib.check(_lib.lib().wc_fcd_phase(B, N, M, _lib.ptr(phasor), _lib.ptr(out), _lib.stream_handle()),
                "wc_fcd_phase")
-    return out[0] if single else out
+    return _args.unbatch(single, out)
 
 
 FCD_KS_CHUNK = 256        # fcd_ks: simulations a pass (bounds the sorted copies)
@@ -745,11 +705,8 @@ def fcd_ks(fcd, emp_values, lag=1):
     fitted on.  fcd [B][nw][nw] or [nw][nw] fp64 device tensor -> [B] (a scalar tensor for one matrix);
     a simulation with a NaN among its selected entries gets NaN.  Plain torch (sort, searchsorted) on the
     device, FCD_KS_CHUNK simulations at a time."""
-    if not isinstance(fcd, torch.Tensor) or fcd.dtype != torch.float64 or fcd.dim() not in (2, 3) \
-            or fcd.shape[-1] != fcd.shape[-2]:
-        raise TypeError("fcd_ks: fcd must be a [B][nw][nw] or [nw][nw] fp64 device tensor")
-    single = fcd.dim() == 2
-    f = fcd[None] if single else fcd
+    f, single, _, _ = _args.stack("fcd_ks", "fcd must be a [B][nw][nw] or [nw][nw] fp64 device tensor", fcd, square=True)
+    f = f[None] if single else f
     nw, lag = f.shape[-1], int(lag)
     if lag < 1 or lag >= nw:
         raise ValueError(f"fcd_ks: lag = {lag} must be in 1 .. nw - 1 = {nw - 1}")
@@ -770,7 +727,7 @@ def fcd_ks(fcd, emp_values, lag=1):
         cdf_e = torch.searchsorted(emp, pooled, right=True).double() / ne
         d = (cdf_a - cdf_e).abs().amax(dim=1)
         out[b0:b0 + FCD_KS_CHUNK] = torch.where(bad, torch.full_like(d, float("nan")), d)
-    return out[0] if single else out
+    return _args.unbatch(single, out)
 
 
 LEIDA_MAX_N = 1024        # wc_leida_eigvec, wc_kmeans_*: a row in one wave's registers
@@ -786,16 +743,14 @@ def leida(x, trim=0):
     of every instantaneous phase-coherence matrix dPC(t)[i][j] = cos(theta_i(t) - theta_j(t))
     (leida_from_phasors) -> (vec [M - 2 trim][B][N], share [M - 2 trim][B]), without B for 2-D input.
     2 <= N <= LEIDA_MAX_N = 1024."""
-    if not isinstance(x, torch.Tensor) or x.dtype != torch.float64 or x.dim() not in (2, 3):
-        raise TypeError("leida: x must be a [M][C] or [M][B][N] fp64 device tensor")
-    single = x.dim() == 2
-    M, B, N = x.shape[0], (1 if single else x.shape[1]), x.shape[-1]
+    x, single, B, N = _args.stack("leida", "x must be a [M][C] or [M][B][N] fp64 device tensor", x, batch=1)
+    M = x.shape[0]
     trim = int(trim)
     Mt = M - 2 * trim
     if B < 1 or N < 2 or N > LEIDA_MAX_N or trim < 0 or M < 2 or Mt < 1:
         raise ValueError(f"leida: needs B >= 1, 2 <= N <= {LEIDA_MAX_N}, trim >= 0, M >= 2 and M - 2 trim >= 1 "
                          f"(N = {N}, B = {B}, M = {M}, trim = {trim})")
-    ph = hilbert_phase(x.reshape(M, B * N).contiguous())[trim:M - trim]
+    ph = hilbert_phase(x.reshape(M, B * N))[trim:M - trim]
     return leida_from_phasors(ph if single else ph.view(Mt, B, N, 2))
 
 
@@ -807,9 +762,8 @@ def leida_from_phasors(phasor):
     of dPC's variance that the vector carries.  dPC = c c^T + s s^T has rank <= 2, so the vector comes
     from the closed-form eigenvector of a 2 x 2 Gram matrix: three dot products a row, nothing N x N.
     A row with lambda1 = lambda2 exactly, or with a NaN or an infinity, is NaN.  2 <= N <= 1024."""
-    if not isinstance(phasor, torch.Tensor) or phasor.dtype != torch.float64 or phasor.dim() not in (3, 4) \
-            or phasor.shape[-1] != 2:
-        raise TypeError("leida_from_phasors: phasor must be a [M][N][2] or [M][B][N][2] fp64 device tensor")
+    _args.tensor("leida_from_phasors", "phasor must be a [M][N][2] or [M][B][N][2] fp64 device tensor", phasor,
+                 torch.float64, (3, 4), last=2)
     N, lead = phasor.shape[-2], tuple(phasor.shape[:-2])
     R = int(np.prod(lead))
     if R < 1 or N < 2 or N > LEIDA_MAX_N:
@@ -824,15 +778,17 @@ def leida_from_phasors(phasor):
     return vec, share
 
 
+def _kmeans_rows(name, x):
+    return _args.tensor(name, "x must be a [R][N] or [M][B][N] fp64 device tensor", x, torch.float64, (2, 3))
+
+
 def _kmeans_args(name, x, centroids, metric):
     """What the k-means functions refuse before they touch the device -> (x as [R][N], centroids
     [K][N], metric code, the leading shape of x)."""
     if metric not in KMEANS_METRICS:
         raise ValueError(f"{name}: unknown metric {metric!r}, must be one of {list(KMEANS_METRICS)}")
-    if not isinstance(x, torch.Tensor) or x.dtype != torch.float64 or x.dim() not in (2, 3):
-        raise TypeError(f"{name}: x must be a [R][N] or [M][B][N] fp64 device tensor")
-    if not isinstance(centroids, torch.Tensor) or centroids.dtype != torch.float64 or centroids.dim() != 2:
-        raise TypeError(f"{name}: centroids must be a [K][N] fp64 device tensor")
+    _kmeans_rows(name, x)
+    _args.tensor(name, "centroids must be a [K][N] fp64 device tensor", centroids, torch.float64, (2,))
     N, K = x.shape[-1], centroids.shape[0]
     if centroids.shape[1] != N:
         raise ValueError(f"{name}: centroids have {centroids.shape[1]} nodes, x has N = {N}")
@@ -856,7 +812,7 @@ def _update(x2, labels, cent, code, ws_bytes=None):
     L = _lib.lib()
     (R, N), K = x2.shape, cent.shape[0]
     nbytes = L.wc_kmeans_workspace_size(R, N, K, code) if ws_bytes is None else int(ws_bytes)
-    ws = torch.empty((max(nbytes, 8) + 7) // 8, dtype=torch.float64, device=x2.device)
+    ws = _args.workspace(nbytes, x2.device)
     new = torch.empty_like(cent)
     count = torch.empty(K, dtype=torch.int64, device=x2.device)
     _lib.check(L.wc_kmeans_update(R, N, K, _lib.ptr(x2), _lib.ptr(labels), _lib.ptr(cent), code, _lib.ptr(new),
@@ -883,8 +839,8 @@ def kmeans_update(x, labels, centroids, metric="cosine", ws_bytes=None):
     KMEANS_UPDATE_BLOCK = 256 rows, added in index order: the bits depend on the shape and the data
     only, not on ws_bytes (default and minimum: wc_kmeans_workspace_size)."""
     x2, cent, code, lead = _kmeans_args("kmeans_update", x, centroids, metric)
-    if not isinstance(labels, torch.Tensor) or labels.dtype != torch.int32 or tuple(labels.shape) != lead:
-        raise TypeError("kmeans_update: labels must be an int32 device tensor shaped as x without its last axis")
+    _args.tensor("kmeans_update", "labels must be an int32 device tensor shaped as x without its last axis", labels,
+                 torch.int32, shapes=(lead,))
     return _update(x2, labels.reshape(-1).contiguous(), cent, code, ws_bytes)
 
 
@@ -917,8 +873,7 @@ def kmeans(x, k_or_init, metric="cosine", max_iter=100, n_init=1, seed=0):
     if max_iter < 0:
         raise ValueError(f"kmeans: max_iter = {max_iter} < 0")
     if inits is None:
-        if not isinstance(x, torch.Tensor) or x.dtype != torch.float64 or x.dim() not in (2, 3):
-            raise TypeError("kmeans: x must be a [R][N] or [M][B][N] fp64 device tensor")
+        _kmeans_rows("kmeans", x)
         x2, _, code, lead = _kmeans_args("kmeans", x, x.reshape(-1, x.shape[-1])[:1], metric)
         pool = torch.nonzero(torch.isfinite(x2).all(dim=1)).reshape(-1).cpu().numpy()
         if pool.size < k:
@@ -948,20 +903,16 @@ def state_stats(labels, k):
     "trans" [B][k][k] (the transition probabilities between consecutive labelled times, self-transitions
     included), without B for 1-D labels.  Counted in integers, divided once; NaN where there is nothing
     to divide by.  A label outside -1 .. k - 1 counts as -1."""
-    if not isinstance(labels, torch.Tensor) or labels.dtype != torch.int32 or labels.dim() not in (1, 2):
-        raise TypeError("state_stats: labels must be a [M][B] or [M] int32 device tensor")
-    k = int(k)
-    single = labels.dim() == 1
-    M, B = labels.shape[0], (1 if single else labels.shape[1])
+    labels, single, B, _ = _args.stack("state_stats", "labels must be a [M][B] or [M] int32 device tensor", labels,
+                                       torch.int32, ndim=2, batch=1)
+    k, M = int(k), labels.shape[0]
     if M < 1 or B < 1 or k < 1 or k > KMEANS_MAX_K:
         raise ValueError(f"state_stats: M = {M}, B = {B}, K = {k}: needs M >= 1, B >= 1 and 1 <= K <= {KMEANS_MAX_K}")
-    labels = labels.contiguous()
     f64 = dict(dtype=torch.float64, device=labels.device)
     occ, dwell, trans = torch.empty((B, k), **f64), torch.empty((B, k), **f64), torch.empty((B, k, k), **f64)
     _lib.check(_lib.lib().wc_state_stats(B, M, k, _lib.ptr(labels), _lib.ptr(occ), _lib.ptr(dwell), _lib.ptr(trans),
                                          _lib.stream_handle()), "wc_state_stats")
-    res = dict(occupancy=occ, dwell=dwell, trans=trans)
-    return {n: v[0] for n, v in res.items()} if single else res
+    return _args.unbatch(single, dict(occupancy=occ, dwell=dwell, trans=trans))
 
 
 def leida_states(vec, centroids, metric="cosine"):
@@ -979,8 +930,7 @@ def state_kl(p, q):
     p [B][K] or [K] and an empirical one q [K] -> [B] (a scalar tensor for one row): the distance a
     sweep is fitted on after LEiDA (Deco et al. 2019).  0 log 0 = 0; an entry that is 0 on one side only
     gives +inf; a row with a NaN gives NaN.  Plain torch, like fcd_ks."""
-    if not isinstance(p, torch.Tensor) or p.dtype != torch.float64 or p.dim() not in (1, 2):
-        raise TypeError("state_kl: p must be a [B][K] or [K] fp64 tensor")
+    _args.tensor("state_kl", "p must be a [B][K] or [K] fp64 tensor", p, torch.float64, (1, 2))
     q = torch.as_tensor(np.asarray(q.cpu() if isinstance(q, torch.Tensor) else q, dtype=np.float64)).to(p.device)
     if q.dim() != 1 or q.shape[0] != p.shape[-1] or q.numel() == 0:
         raise ValueError(f"state_kl: q must be one row of K = {p.shape[-1]} entries")
@@ -1026,7 +976,6 @@ def _welch_args(name, T, device, fs, window, nperseg, noverlap, detrend, scaling
     """SciPy's coercion of the arguments welch, csd and coherence share, for a series of T samples ->
     (detrend flag, window tensor [nperseg], nperseg, noverlap, scale, freqs); name prefixes the
     messages; stacklevel makes the clamped-nperseg warning point at the public function's caller."""
-    import warnings
     from scipy import fft as sp_fft
     if detrend == "constant":
         det = 1
@@ -1079,8 +1028,7 @@ def welch(x, fs=1.0, window="hann", nperseg=None, noverlap=None, detrend="consta
     SciPy's UserWarning.  detrend: "constant" or False.  scaling: "density" or "spectrum".
     ws_bytes: workspace size (default: what all columns want, at most WELCH_PSD_WS_CAP, never
     below the minimum); the result does not depend on it."""
-    if x.dtype != torch.float64 or x.dim() < 2:
-        raise TypeError("welch: x must be a [T][C] or [T][B][N] fp64 device tensor")
+    _args.tensor("welch", "x must be a [T][C] or [T][B][N] fp64 device tensor", x, torch.float64, _FROM_2D)
     T = x.shape[0]
     det, win, nperseg, noverlap, scale, freqs = _welch_args("welch", T, x.device, fs, window, nperseg, noverlap,
                                                             detrend, scaling)
@@ -1093,10 +1041,10 @@ def welch(x, fs=1.0, window="hann", nperseg=None, noverlap=None, detrend="consta
     if ws_bytes is None and need:
         nseg = (T - nperseg) // (nperseg - noverlap) + 1
         sb = 2 * -(-nseg // 32)                   # segments per block; -(-nseg // sb) blocks of F doubles a column
-        ws_bytes = max(need, min(need + (C - 1) * -(-nseg // sb) * F * 8, WELCH_PSD_WS_CAP))
+        ws_bytes = _args.ws_default(need, need + (C - 1) * -(-nseg // sb) * F * 8, WELCH_PSD_WS_CAP)
     ws_bytes = ws_bytes or 16                     # need == 0: the call says why
     psd = torch.empty((F, C), dtype=torch.float64, device=x.device)
-    ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.float64, device=x.device)
+    ws = _args.workspace(ws_bytes, x.device)
     _lib.check(L.wc_welch_psd(C, T, _lib.ptr(x2), nperseg, noverlap, _lib.ptr(win), det, scale, _lib.ptr(psd),
                               _lib.ptr(ws), ws_bytes, _lib.stream_handle()), "wc_welch_psd")
     return freqs, psd.reshape((F,) + tuple(x.shape[1:]))
@@ -1107,10 +1055,10 @@ CSD_MATRIX, CSD_COHERENCE, CSD_PAIRS, CSD_PAIR_COHERENCE = 0, 1, 2, 3
 
 
 def _csd(name, coh, x, y, fs, window, nperseg, noverlap, detrend, scaling, ws_bytes):
-    if x.dtype != torch.float64 or x.dim() != 2:
-        raise TypeError(f"{name}: x must be a [T][C] fp64 device tensor")
-    if y is not None and (y.dtype != torch.float64 or y.shape != x.shape or y.device != x.device):
-        raise TypeError(f"{name}: y must be an fp64 tensor of x's shape on x's device")
+    _args.tensor(name, "x must be a [T][C] fp64 device tensor", x, torch.float64, (2,))
+    if y is not None:
+        _args.tensor(name, "y must be an fp64 tensor of x's shape on x's device", y, torch.float64,
+                     shapes=(tuple(x.shape),), device=x.device)
     T = x.shape[0]
     det, win, nperseg, noverlap, scale, freqs = _welch_args(name, T, x.device, fs, window, nperseg, noverlap,
                                                             detrend, scaling, stacklevel=4)
@@ -1122,11 +1070,11 @@ def _csd(name, coh, x, y, fs, window, nperseg, noverlap, detrend, scaling, ws_by
     need = L.wc_csd_workspace_size(C, T, nperseg, noverlap)
     if ws_bytes is None and need:
         nseg = (T - nperseg) // (nperseg - noverlap) + 1
-        ws_bytes = max(need, min(need + (-(-nseg // 2) - 1) * 2 * F * C * 16, CSD_WS_CAP))  # all segment pairs
+        ws_bytes = _args.ws_default(need, need + (-(-nseg // 2) - 1) * 2 * F * C * 16, CSD_WS_CAP)  # all segment pairs
     ws_bytes = ws_bytes or 16                     # need == 0: the call says why
     shape = (F, x.shape[1], x.shape[1]) if y is None else (F, x.shape[1])
     out = torch.empty(shape, dtype=torch.float64 if coh else torch.complex128, device=x.device)
-    ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.float64, device=x.device)
+    ws = _args.workspace(ws_bytes, x.device)
     _lib.check(L.wc_csd(C, T, _lib.ptr(x2), nperseg, noverlap, _lib.ptr(win), det, scale, mode, _lib.ptr(out),
                         _lib.ptr(ws), ws_bytes, _lib.stream_handle()), "wc_csd")
     return freqs, out
@@ -1177,8 +1125,7 @@ def spectrogram(x, fs=1.0, window=("tukey", 0.25), nperseg=None, noverlap=None, 
                                   "utils.spectrogram unwraps the device's angles on the host")
     if mode not in SPEC_MODES:
         raise ValueError(f"unknown value for mode {mode}, must be one of {list(SPEC_MODES) + ['phase']}")
-    if x.dtype != torch.float64 or x.dim() < 2:
-        raise TypeError("spectrogram: x must be a [T][C] or [T][B][N] fp64 device tensor")
+    _args.tensor("spectrogram", "x must be a [T][C] or [T][B][N] fp64 device tensor", x, torch.float64, _FROM_2D)
     T = x.shape[0]
     det, win, nperseg, nov, scale, freqs = _welch_args("spectrogram", T, x.device, fs, window, nperseg, noverlap,
                                                        detrend, scaling)
@@ -1194,7 +1141,7 @@ def spectrogram(x, fs=1.0, window=("tukey", 0.25), nperseg=None, noverlap=None, 
     S = (T - nperseg) // step + 1 if T >= nperseg else 0
     ws_bytes = L.wc_spectrogram_workspace_size(nperseg) or 16  # 0: the call says why
     out = torch.empty((S, F, C), dtype=torch.complex128 if mode == "complex" else torch.float64, device=x.device)
-    ws = torch.empty(ws_bytes // 8, dtype=torch.float64, device=x.device)
+    ws = _args.workspace(ws_bytes, x.device)
     _lib.check(L.wc_spectrogram(C, T, _lib.ptr(x2), nperseg, nov, _lib.ptr(win), det, scale, SPEC_MODES[mode],
                                 _lib.ptr(out), _lib.ptr(ws), ws_bytes, _lib.stream_handle()), "wc_spectrogram")
     return freqs, times, out.view((S, F) + tuple(x.shape[1:])).movedim(0, -1)
@@ -1202,17 +1149,6 @@ def spectrogram(x, fs=1.0, window=("tukey", 0.25), nperseg=None, noverlap=None, 
 
 CONN_BITS = {"plv": 1, "pli": 2, "wpli": 4, "aec_orth": 8}  # WC_CONN_*, the order of wc_phase_conn's out
 CONN_MEASURES = ("plv", "pli", "wpli", "aec", "aec_orth")
-
-
-def _conn_measures(name, measures):
-    """The requested measures as a tuple of known names, each once."""
-    names = (measures,) if isinstance(measures, str) else tuple(measures)
-    for m in names:
-        if m not in CONN_MEASURES:
-            raise ValueError(f"{name}: unknown measure {m!r}, must be one of {list(CONN_MEASURES)}")
-    if not names:
-        raise ValueError(f"{name}: no measure asked for, choose from {list(CONN_MEASURES)}")
-    return tuple(dict.fromkeys(names))
 
 
 AEC_GROUP = 48      # _aec_corrcoef: columns per group, two groups a wc_corrcoef call (its N <= 96 kernels)
@@ -1252,19 +1188,16 @@ def phase_connectivity_from(phasor, amp=None, measures=CONN_MEASURES, ws_bytes=N
     the diagonals are 1 (plv, aec) and 0.  A zero denominator gives NaN (wpli and aec_orth of two
     identical columns, a constant envelope).  ws_bytes: workspace size (default and least: the
     minimum); the result does not depend on it."""
-    names = _conn_measures("phase_connectivity_from", measures)
-    if not isinstance(phasor, torch.Tensor) or phasor.dtype != torch.float64 or phasor.dim() not in (3, 4) \
-            or phasor.shape[-1] != 2:
-        raise TypeError("phase_connectivity_from: phasor must be a [T][C][2] or [T][B][N][2] fp64 device tensor")
+    names = _args.names("phase_connectivity_from", measures, CONN_MEASURES)
+    phasor, single, B, N = _args.stack("phase_connectivity_from", "phasor must be a [T][C][2] or [T][B][N][2] fp64 "
+                                       "device tensor", phasor, ndim=4, batch=1, last=2)
     need_amp = any(m in ("wpli", "aec", "aec_orth") for m in names)
-    if need_amp and (not isinstance(amp, torch.Tensor) or amp.dtype != torch.float64
-                     or amp.shape != phasor.shape[:-1] or amp.device != phasor.device):
-        raise TypeError("phase_connectivity_from: wpli, aec and aec_orth need amp, an fp64 tensor of the "
-                        "phasors' [T][C] or [T][B][N] on their device")
+    if need_amp:
+        _args.tensor("phase_connectivity_from", "wpli, aec and aec_orth need amp, an fp64 tensor of the phasors' "
+                     "[T][C] or [T][B][N] on their device", amp, torch.float64, shapes=(tuple(phasor.shape[:-1]),),
+                     device=phasor.device)
     M = phasor.shape[0]
-    B, N = (1, phasor.shape[1]) if phasor.dim() == 3 else (phasor.shape[1], phasor.shape[2])
-    shape = (N, N) if phasor.dim() == 3 else (B, N, N)
-    phasor = phasor.contiguous()
+    shape = (N, N) if single else (B, N, N)
     amp = amp.contiguous() if need_amp else None
     res = {}
     bits = sum(CONN_BITS[m] for m in names if m in CONN_BITS)
@@ -1272,7 +1205,7 @@ def phase_connectivity_from(phasor, amp=None, measures=CONN_MEASURES, ws_bytes=N
         L = _lib.lib()
         need = L.wc_phase_conn_workspace_size(B, N, M, bits)
         nbytes = max(need, ws_bytes or 0) or 16      # need == 0: the call says why
-        ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=phasor.device)
+        ws = _args.workspace(nbytes, phasor.device)
         got = [m for m in CONN_BITS if CONN_BITS[m] & bits]  # ascending bit order
         out = torch.empty((len(got), B, N, N), dtype=torch.float64, device=phasor.device)
         _lib.check(L.wc_phase_conn(B, N, M, _lib.ptr(phasor), _lib.ptr(amp if bits & 12 else None), bits,
@@ -1302,9 +1235,8 @@ def phase_connectivity(x, measures=CONN_MEASURES):
     no logarithm), all from z = scipy.signal.hilbert(x, axis=0): the phasors z / |z| through
     hilbert_phase, the envelopes |z| (only where a measure needs them) through hilbert_envelope,
     each with its own dispatch.  2 <= T <= 524288, N <= 1024; see phase_connectivity_from."""
-    names = _conn_measures("phase_connectivity", measures)
-    if not isinstance(x, torch.Tensor) or x.dtype != torch.float64 or x.dim() not in (2, 3):
-        raise TypeError("phase_connectivity: x must be a [T][C] or [T][B][N] fp64 device tensor")
+    names = _args.names("phase_connectivity", measures, CONN_MEASURES)
+    _args.tensor("phase_connectivity", "x must be a [T][C] or [T][B][N] fp64 device tensor", x, torch.float64, (2, 3))
     T = x.shape[0]
     x2 = x.reshape(T, -1).contiguous()
     ph = hilbert_phase(x2).view(tuple(x.shape) + (2,))
@@ -1330,7 +1262,7 @@ def corrcoef(x, B, N):
     x = x.contiguous()
     M = x.shape[0]
     fc = torch.empty((B, N, N), dtype=torch.float64, device=x.device)
-    ws = torch.empty(L.wc_corrcoef_workspace_size(B, N, M) // 8 + 1, dtype=torch.float64, device=x.device)
-    _lib.check(L.wc_corrcoef(B, N, M, _lib.ptr(x), _lib.ptr(fc), _lib.ptr(ws), ws.numel() * 8,
-                             _lib.stream_handle()), "wc_corrcoef")
+    ws_bytes = (L.wc_corrcoef_workspace_size(B, N, M) // 8 + 1) * 8   # the minimum, rounded up past a multiple of 8
+    _lib.check(L.wc_corrcoef(B, N, M, _lib.ptr(x), _lib.ptr(fc), _lib.ptr(_args.workspace(ws_bytes, x.device)),
+                             ws_bytes, _lib.stream_handle()), "wc_corrcoef")
     return fc

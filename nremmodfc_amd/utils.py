@@ -16,7 +16,7 @@ the pandas / plot helpers find_extreme and xy2plotcor.
 import numpy as np
 import torch
 
-from . import sigchain
+from . import _args, sigchain
 
 device = "cuda"
 
@@ -86,36 +86,72 @@ def envelope(series, dt=0.002, freqs=[8, 13], fcut=None):
     return sigchain.envelope(xt, dt, tuple(freqs), fcut).cpu().numpy().reshape(x.shape)
 
 
+def _refuse_nfft(name, x, window, nperseg, nfft, axis):
+    """nfft may only restate the segment length SciPy would use."""
+    if nfft is None:
+        return
+    named = isinstance(window, (str, tuple))
+    seg = int(nperseg) if nperseg is not None else (256 if named else len(window))
+    if named:
+        seg = min(seg, np.shape(x)[axis])  # SciPy clamps a named window's nperseg to the input
+    if int(nfft) != seg:
+        raise NotImplementedError(f"{name}: nfft other than nperseg (zero padding) does not run on the device")
+
+
+def _refuse_detrend(name, detrend):
+    if not (detrend is False or (isinstance(detrend, str) and detrend == 'constant')):
+        raise NotImplementedError(f"{name}: detrend = {detrend!r} (only 'constant' and False run on the device)")
+
+
+def _refuse_options(name, return_onesided, average, detrend):
+    if not return_onesided:
+        raise NotImplementedError(f"{name}: return_onesided=False does not run on the device")
+    if average != 'mean':
+        raise NotImplementedError(f"{name}: average = {average!r} (only 'mean' runs on the device)")
+    _refuse_detrend(name, detrend)
+
+
+def _real_input(name, x, noun="input"):
+    x = np.asarray(x)
+    if np.iscomplexobj(x):
+        raise NotImplementedError(f"{name}: complex {noun} does not run on the device")
+    return x
+
+
+def _not_empty(name, x):
+    if x.ndim < 1 or x.size == 0:
+        raise ValueError(f"{name}: x must have at least one sample")
+
+
+def _upload(a, to=None):
+    """a as a contiguous fp64 tensor on the module's device, or on `to`."""
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(device if to is None else to)
+
+
+def _time_major(x, axis):
+    """x with `axis` first and the others flattened, on the device as fp64, and the others' shape."""
+    xt = np.moveaxis(x, axis, 0)
+    return _upload(xt.reshape(xt.shape[0], -1)), xt.shape[1:]
+
+
+def _from_time_major(out, rest, axis):
+    p = out.cpu().numpy().reshape((out.shape[0],) + rest)
+    return np.moveaxis(p, 0, axis) if rest else p
+
+
 def welch(x, fs=1.0, window='hann', nperseg=None, noverlap=None, nfft=None, detrend='constant',
           return_onesided=True, scaling='density', axis=-1, average='mean'):
     """scipy.signal.welch with its parameter order and defaults, on the device (wc_welch_psd), for
     what cortex_run.py:203-209 asks of it: real input, one-sided, mean over segments, no nfft
     padding, detrend 'constant' or False, 2 <= nperseg <= 4096.  numpy in, numpy (freqs, Pxx) out,
     shaped as SciPy's; anything else SciPy's welch offers raises NotImplementedError."""
-    if nfft is not None:
-        named = isinstance(window, (str, tuple))
-        seg = int(nperseg) if nperseg is not None else (256 if named else len(window))
-        if named:
-            seg = min(seg, np.shape(x)[axis])  # SciPy clamps a named window's nperseg to the input
-    if nfft is not None and int(nfft) != seg:
-        raise NotImplementedError("welch: nfft other than nperseg (zero padding) does not run on the device")
-    if not return_onesided:
-        raise NotImplementedError("welch: return_onesided=False does not run on the device")
-    if average != 'mean':
-        raise NotImplementedError(f"welch: average = {average!r} (only 'mean' runs on the device)")
-    if not (detrend is False or (isinstance(detrend, str) and detrend == 'constant')):
-        raise NotImplementedError(f"welch: detrend = {detrend!r} (only 'constant' and False run on the device)")
-    x = np.asarray(x)
-    if np.iscomplexobj(x):
-        raise NotImplementedError("welch: complex input x does not run on the device")
-    if x.ndim < 1 or x.size == 0:
-        raise ValueError("welch: x must have at least one sample")
-    xt = np.moveaxis(x, axis, 0)
-    rest = xt.shape[1:]
-    xd = torch.as_tensor(np.ascontiguousarray(xt.reshape(xt.shape[0], -1), dtype=np.float64)).to(device)
+    _refuse_nfft("welch", x, window, nperseg, nfft, axis)
+    _refuse_options("welch", return_onesided, average, detrend)
+    x = _real_input("welch", x, "input x")
+    _not_empty("welch", x)
+    xd, rest = _time_major(x, axis)
     freqs, psd = sigchain.welch(xd, fs, window, nperseg, noverlap, detrend, scaling)
-    pxx = psd.cpu().numpy().reshape((psd.shape[0],) + rest)
-    return freqs, np.moveaxis(pxx, 0, axis) if rest else pxx
+    return freqs, _from_time_major(psd, rest, axis)
 
 
 def spectrogram(x, fs=1.0, window=('tukey', .25), nperseg=None, noverlap=None, nfft=None, detrend='constant',
@@ -131,27 +167,11 @@ def spectrogram(x, fs=1.0, window=('tukey', .25), nperseg=None, noverlap=None, n
     modes = ['psd', 'complex', 'magnitude', 'angle', 'phase']
     if mode not in modes:
         raise ValueError(f'unknown value for mode {mode}, must be one of {modes}')
-    if nfft is not None:
-        named = isinstance(window, (str, tuple))
-        seg = int(nperseg) if nperseg is not None else (256 if named else len(window))
-        if named:
-            seg = min(seg, np.shape(x)[axis])  # SciPy clamps a named window's nperseg to the input
-        if int(nfft) != seg:
-            raise NotImplementedError("spectrogram: nfft other than nperseg (zero padding) does not run on the "
-                                      "device")
-    if not return_onesided:
-        raise NotImplementedError("spectrogram: return_onesided=False does not run on the device")
-    if not (detrend is False or (isinstance(detrend, str) and detrend == 'constant')):
-        raise NotImplementedError(f"spectrogram: detrend = {detrend!r} (only 'constant' and False run on the "
-                                  "device)")
-    x = np.asarray(x)
-    if np.iscomplexobj(x):
-        raise NotImplementedError("spectrogram: complex input x does not run on the device")
-    if x.ndim < 1 or x.size == 0:
-        raise ValueError("spectrogram: x must have at least one sample")
-    xt = np.moveaxis(x, axis, 0)
-    rest = xt.shape[1:]
-    xd = torch.as_tensor(np.ascontiguousarray(xt.reshape(xt.shape[0], -1), dtype=np.float64)).to(device)
+    _refuse_nfft("spectrogram", x, window, nperseg, nfft, axis)
+    _refuse_options("spectrogram", return_onesided, 'mean', detrend)
+    x = _real_input("spectrogram", x, "input x")
+    _not_empty("spectrogram", x)
+    xd, rest = _time_major(x, axis)
     freqs, times, sxx = sigchain.spectrogram(xd, fs, window, nperseg, noverlap, detrend, scaling,
                                              'angle' if mode == 'phase' else mode)
     sxx = sxx.cpu().numpy().reshape((sxx.shape[0],) + rest + (sxx.shape[-1],))
@@ -165,36 +185,15 @@ def spectrogram(x, fs=1.0, window=('tukey', .25), nperseg=None, noverlap=None, n
 def _cross_input(name, x, y, window, nperseg, nfft, detrend, axis, return_onesided=True, average='mean'):
     """What csd and coherence refuse before they touch the device, and x, y as (time, columns)
     device tensors with the shape of the remaining axes."""
-    x, y = np.asarray(x), np.asarray(y)
-    if np.iscomplexobj(x) or np.iscomplexobj(y):
-        raise NotImplementedError(f"{name}: complex input does not run on the device")
+    x, y = _real_input(name, x), _real_input(name, y)
     if x.shape != y.shape:
         raise NotImplementedError(f"{name}: x and y of different shapes or lengths (broadcasting, zero padding of the "
                                   "shorter) do not run on the device")
-    if x.ndim < 1 or x.size == 0:
-        raise ValueError(f"{name}: x must have at least one sample")
-    if nfft is not None:
-        named = isinstance(window, (str, tuple))
-        seg = int(nperseg) if nperseg is not None else (256 if named else len(window))
-        if named:
-            seg = min(seg, x.shape[axis])  # SciPy clamps a named window's nperseg to the input
-        if int(nfft) != seg:
-            raise NotImplementedError(f"{name}: nfft other than nperseg (zero padding) does not run on the device")
-    if not return_onesided:
-        raise NotImplementedError(f"{name}: return_onesided=False does not run on the device")
-    if average != 'mean':
-        raise NotImplementedError(f"{name}: average = {average!r} (only 'mean' runs on the device)")
-    if not (detrend is False or (isinstance(detrend, str) and detrend == 'constant')):
-        raise NotImplementedError(f"{name}: detrend = {detrend!r} (only 'constant' and False run on the device)")
-    xt, yt = np.moveaxis(x, axis, 0), np.moveaxis(y, axis, 0)
-    rest = xt.shape[1:]
-    up = lambda a: torch.from_numpy(np.array(a.reshape(a.shape[0], -1), dtype=np.float64, order="C")).to(device)
-    return up(xt), up(yt), rest
-
-
-def _cross_output(out, rest, axis):
-    p = out.cpu().numpy().reshape((out.shape[0],) + rest)
-    return np.moveaxis(p, 0, axis) if rest else p
+    _not_empty(name, x)
+    _refuse_nfft(name, x, window, nperseg, nfft, axis)
+    _refuse_options(name, return_onesided, average, detrend)
+    (xd, rest), (yd, _) = _time_major(x, axis), _time_major(y, axis)
+    return xd, yd, rest
 
 
 def csd(x, y, fs=1.0, window='hann', nperseg=None, noverlap=None, nfft=None, detrend='constant',
@@ -205,7 +204,7 @@ def csd(x, y, fs=1.0, window='hann', nperseg=None, noverlap=None, nfft=None, det
     SciPy's; anything else SciPy's csd offers raises NotImplementedError."""
     xd, yd, rest = _cross_input("csd", x, y, window, nperseg, nfft, detrend, axis, return_onesided, average)
     freqs, p = sigchain.csd(xd, yd, fs, window, nperseg, noverlap, detrend, scaling)
-    return freqs, _cross_output(p, rest, axis)
+    return freqs, _from_time_major(p, rest, axis)
 
 
 def coherence(x, y, fs=1.0, window='hann', nperseg=None, noverlap=None, nfft=None, detrend='constant', axis=-1):
@@ -213,18 +212,15 @@ def coherence(x, y, fs=1.0, window='hann', nperseg=None, noverlap=None, nfft=Non
     mode), under csd's restrictions.  numpy in, numpy (freqs, Cxy) out."""
     xd, yd, rest = _cross_input("coherence", x, y, window, nperseg, nfft, detrend, axis)
     freqs, c = sigchain.coherence(xd, yd, fs, window, nperseg, noverlap, detrend)
-    return freqs, _cross_output(c, rest, axis)
+    return freqs, _from_time_major(c, rest, axis)
 
 
 def _matrix_input(name, x, detrend):
-    x = np.asarray(x)
-    if np.iscomplexobj(x):
-        raise NotImplementedError(f"{name}: complex input does not run on the device")
-    if not (detrend is False or (isinstance(detrend, str) and detrend == 'constant')):
-        raise NotImplementedError(f"{name}: detrend = {detrend!r} (only 'constant' and False run on the device)")
+    x = _real_input(name, x)
+    _refuse_detrend(name, detrend)
     if x.ndim != 2 or x.size == 0:
         raise ValueError(f"{name}: x must be (time, rois)")
-    return torch.from_numpy(np.array(x, dtype=np.float64, order="C")).to(device)
+    return _upload(x)
 
 
 def csd_matrix(x, fs=1.0, window='hann', nperseg=None, noverlap=None, detrend='constant', scaling='density'):
@@ -244,6 +240,26 @@ def coherence_matrix(x, fs=1.0, window='hann', nperseg=None, noverlap=None, detr
     return freqs, c.cpu().numpy()
 
 
+def _series(name, series, freqs=None):
+    """series as a host array of real numbers, (time, rois) or (time, B, N), not empty; freqs, if given, a band."""
+    x = np.asarray(series)
+    if x.dtype.kind not in "fiub":
+        raise TypeError(f"{name}: series must be real numbers, not {x.dtype}")
+    if x.ndim not in (2, 3) or x.size == 0:
+        raise ValueError("series must be (time, rois) or (time, B, N)")
+    if freqs is not None and len(freqs) != 2:
+        raise ValueError("freqs must be [fmin, fmax] or None")
+    return x
+
+
+def _band_limited(xt, dt, freqs):
+    """utils.envelope's Bessel order-3 band-pass filtfilt over freqs; freqs None: xt as it is."""
+    if freqs is None:
+        return xt
+    (bb, ba), _ = sigchain.envelope_filters(float(dt), float(freqs[0]), float(freqs[1]), None)
+    return sigchain.filtfilt(bb, ba, xt)
+
+
 def connectivity(series, dt=0.002, freqs=[8, 13], measures=("plv", "pli", "wpli", "aec", "aec_orth"),
                  device="cuda"):
     """Phase and envelope connectivity of series (time, rois) or (time, B, N) in a band: utils.envelope's
@@ -254,18 +270,8 @@ def connectivity(series, dt=0.002, freqs=[8, 13], measures=("plv", "pli", "wpli"
     orthogonalised form (sigchain.phase_connectivity).  numpy in (float32 accepted), a dict of
     numpy arrays (rois, rois) or (B, N, N) out.  time <= 524288 (with a band-pass: >= 22, the
     order-6 filter's padlen is 21), N <= 1024."""
-    names = sigchain._conn_measures("connectivity", measures)
-    x = np.asarray(series)
-    if x.dtype.kind not in "fiub":
-        raise TypeError(f"connectivity: series must be real numbers, not {x.dtype}")
-    if x.ndim not in (2, 3) or x.size == 0:
-        raise ValueError("series must be (time, rois) or (time, B, N)")
-    if freqs is not None and len(freqs) != 2:
-        raise ValueError("freqs must be [fmin, fmax] or None")
-    xt = torch.from_numpy(np.array(x, dtype=np.float64, order="C")).to(device)
-    if freqs is not None:
-        (bb, ba), _ = sigchain.envelope_filters(float(dt), float(freqs[0]), float(freqs[1]), None)
-        xt = sigchain.filtfilt(bb, ba, xt)
+    names = _args.names("connectivity", measures, sigchain.CONN_MEASURES)
+    xt = _band_limited(_upload(_series("connectivity", series, freqs), device), dt, freqs)
     return {m: v.cpu().numpy() for m, v in sigchain.phase_connectivity(xt, names).items()}
 
 
@@ -277,14 +283,10 @@ def fcd(series, window=30, step=1, method="corr", trim=0, device="cuda"):
     already band-limited series, less `trim` samples at either end -> (time - 2 trim, time - 2 trim)
     or with a leading B; window and step are not used.  numpy in (float32 accepted), numpy out.
     3 <= N <= 96 (phase: 2), nw and time - 2 trim <= 4096."""
-    x = np.asarray(series)
-    if x.dtype.kind not in "fiub":
-        raise TypeError(f"fcd: series must be real numbers, not {x.dtype}")
-    if x.ndim not in (2, 3) or x.size == 0:
-        raise ValueError("series must be (time, rois) or (time, B, N)")
+    x = _series("fcd", series)
     if method not in sigchain.FCD_METHODS:
         raise ValueError(f"fcd: unknown method {method!r}, must be one of {list(sigchain.FCD_METHODS)}")
-    xt = torch.from_numpy(np.array(x, dtype=np.float64, order="C")).to(device)
+    xt = _upload(x, device)
     if method == "phase":
         return sigchain.fcd(xt, method="phase", trim=trim).cpu().numpy()
     return sigchain.fcd(xt, window, step).cpu().numpy()
@@ -299,13 +301,7 @@ def leida(series, dt, freqs, centroids=None, k=None, trim=0, metric="cosine", de
     (K, N) also sigchain.leida_states' "labels", "occupancy", "dwell" and "trans"; with an integer k
     instead, the eigenvectors of all simulations and times are clustered first (sigchain.kmeans, seed 0)
     and "centroids", "inertia" and "n_iter" are returned too.  2 <= N <= 1024, K <= 32."""
-    x = np.asarray(series)
-    if x.dtype.kind not in "fiub":
-        raise TypeError(f"leida: series must be real numbers, not {x.dtype}")
-    if x.ndim not in (2, 3) or x.size == 0:
-        raise ValueError("series must be (time, rois) or (time, B, N)")
-    if freqs is not None and len(freqs) != 2:
-        raise ValueError("freqs must be [fmin, fmax] or None")
+    x = _series("leida", series, freqs)
     if metric not in sigchain.KMEANS_METRICS:
         raise ValueError(f"leida: unknown metric {metric!r}, must be one of {list(sigchain.KMEANS_METRICS)}")
     if centroids is not None and k is not None:
@@ -320,11 +316,7 @@ def leida(series, dt, freqs, centroids=None, k=None, trim=0, metric="cosine", de
     if N < 2 or N > sigchain.LEIDA_MAX_N or int(trim) < 0 or x.shape[0] - 2 * int(trim) < 1:
         raise ValueError(f"leida: needs 2 <= N <= {sigchain.LEIDA_MAX_N}, trim >= 0 and time - 2 trim >= 1 "
                          f"(N = {N}, time = {x.shape[0]}, trim = {trim})")
-    xt = torch.from_numpy(np.array(x, dtype=np.float64, order="C")).to(device)
-    if freqs is not None:
-        (bb, ba), _ = sigchain.envelope_filters(float(dt), float(freqs[0]), float(freqs[1]), None)
-        xt = sigchain.filtfilt(bb, ba, xt)
-    vec, share = sigchain.leida(xt, trim)
+    vec, share = sigchain.leida(_band_limited(_upload(x, device), dt, freqs), trim)
     res = dict(vec=vec, share=share)
     if k is not None:
         cent, _, inertia, n_iter = sigchain.kmeans(vec, int(k), metric)
