@@ -1,6 +1,6 @@
 // wc_device.h -- device helpers shared by the Wilson-Cowan integrators (gfx950):
 // the Philox4x32-10 noise stream of include/wcsde.h, Box-Muller normals,
-// precision traits (sigmoid, MFMA), the 3-way bf16 split and the compensated
+// precision traits (sigmoid, MFMA), the two-part fp16 split and the compensated
 // a_ie accumulator.  Both wc_sde.hip (N <= 96, register-resident) and
 // wc_sde_large.hip (N > 96, one launch per step) draw the SAME normals for a
 // given (key, step, node), so the two paths integrate the same stochastic
@@ -14,8 +14,6 @@ namespace wcdev {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef double f64x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 
@@ -114,10 +112,6 @@ __device__ __forceinline__ void quad_normals(uint64_t step, uint32_t q, uint64_t
     quad_normals_raw(step, q, key, z);
 #pragma unroll
     for (int i = 0; i < 4; ++i) z[i] *= kSqrt2Ln2;
-}
-template <typename Coef>
-__device__ __forceinline__ void quad_normals(uint64_t step, uint32_t q, uint64_t key, float z[4], Coef) {
-    quad_normals(step, q, key, z);
 }
 
 // ---------------- fp64 elementary functions for the parity path ----------------
@@ -278,18 +272,11 @@ __device__ __forceinline__ void quad_normals(uint64_t step, uint32_t q, uint64_t
 template <typename Real> struct Tr;
 template <> struct Tr<float> {
     typedef f32x4 acc_t;
-    __device__ static __forceinline__ acc_t mfma(float a, float b, acc_t c) {
-        return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-    }
     // logistic 1/(1+exp(-(x-mu)*sigma)) with sl = sigma*log2(e) precomputed
     __device__ static __forceinline__ float sig(float x, float mu, float sl) {
         return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f((mu - x) * sl));
     }
-    template <typename Coef>
-    __device__ static __forceinline__ float sig(float x, float mu, float sl, Coef) { return sig(x, mu, sl); }
     __device__ static __forceinline__ float slope(double s) { return (float)(s * 1.4426950408889634); }
-    // C/D row of a 16x16x4 f32 tile is (lane>>4)*4 + reg: identity row->node map
-    __host__ __device__ static __forceinline__ int row_node(int rho) { return rho; }
 };
 template <> struct Tr<double> {
     typedef f64x4 acc_t;
@@ -308,27 +295,6 @@ template <> struct Tr<double> {
     // register r still means node 4g + r of the tile
     __host__ __device__ static __forceinline__ int row_node(int rho) { return 4 * (rho & 3) + (rho >> 2); }
 };
-
-// v = hi + mid + lo, each a bf16: |v - hi - mid - lo| <= 2^-27 |v|
-__device__ __forceinline__ void split3(const float v[4], bf16x4& hi, bf16x4& mid, bf16x4& lo) {
-    // pairwise: one v_cvt_pk_bf16_f32 (RNE) per two values and part, residuals by packed subtracts
-    typedef float f2 __attribute__((ext_vector_type(2)));
-    typedef __bf16 b2 __attribute__((ext_vector_type(2)));
-#pragma unroll
-    for (int p = 0; p < 2; ++p) {
-        const f2 x = {v[2 * p], v[2 * p + 1]};
-        const b2 h = __builtin_convertvector(x, b2);
-        const f2 r = x - __builtin_convertvector(h, f2);
-        const b2 m = __builtin_convertvector(r, b2);
-        const b2 l = __builtin_convertvector(r - __builtin_convertvector(m, f2), b2);
-        hi[2 * p] = h[0];
-        hi[2 * p + 1] = h[1];
-        mid[2 * p] = m[0];
-        mid[2 * p + 1] = m[1];
-        lo[2 * p] = l[0];
-        lo[2 * p + 1] = l[1];
-    }
-}
 
 // fp16 two-part split of v * 2^10 (v in [0, 1]): hi = fp16(RNE), lo = fp16(v 2^10 - hi);
 // v 2^10 - hi is exact in fp32, so hi + lo carries 22 significant bits and, scaled,
@@ -372,35 +338,7 @@ __device__ __forceinline__ void split2h_pair(const float v[2], uint32_t& hi, uin
     lo = lb;
 }
 
-// fp16 three-part split of v * 2^10 (the V_F16X6 A/B): hi = fp16(x), r = x - hi exact in fp32 (one
-// v_fma_mix_f32 per value), mid = fp16(r), lo = fp16(r - mid) (v_fma_mix{lo,hi}_f16, rounded once)
-template <bool PRE = false>
-__device__ __forceinline__ void split3h(const float v[4], f16x4& hi, f16x4& mid, f16x4& lo) {
-    typedef float f2 __attribute__((ext_vector_type(2)));
-    typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-#pragma unroll
-    for (int p = 0; p < 2; ++p) {
-        const f2 x = PRE ? (f2){v[2 * p], v[2 * p + 1]} : (f2){v[2 * p], v[2 * p + 1]} * 1024.0f;
-        const h2 h = __builtin_convertvector(x, h2);
-        float r0, r1;
-        asm("v_fma_mix_f32 %0, %1, 1.0, -%2 op_sel_hi:[0,0,1]" : "=v"(r0) : "v"(x[0]), "v"(h));
-        asm("v_fma_mix_f32 %0, %1, 1.0, -%2 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "=v"(r1) : "v"(x[1]), "v"(h));
-        const f2 r = {r0, r1};
-        const h2 m = __builtin_convertvector(r, h2);
-        uint32_t lb;
-        asm("v_fma_mixlo_f16 %0, %1, 1.0, -%2 op_sel_hi:[0,0,1]" : "=v"(lb) : "v"(r[0]), "v"(m));
-        asm("v_fma_mixhi_f16 %0, %1, 1.0, -%2 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(lb) : "v"(r[1]), "v"(m));
-        const h2 l = __builtin_bit_cast(h2, lb);
-        hi[2 * p] = h[0];
-        hi[2 * p + 1] = h[1];
-        mid[2 * p] = m[0];
-        mid[2 * p + 1] = m[1];
-        lo[2 * p] = l[0];
-        lo[2 * p + 1] = l[1];
-    }
-}
-
-// Plasticity variable a_ie: fp64, or a compensated fp32 pair (increments of
+// Plasticity variable a_ie: fp64 on the fp64 path, a compensated fp32 pair on the fp32 paths (increments of
 // ~1e-6 on a ~2.5 are below fp32 half-ulp: plain fp32 would drop them).
 template <bool kPair> struct AccA;
 template <> struct AccA<false> {
@@ -408,7 +346,6 @@ template <> struct AccA<false> {
     __device__ void set(double x) { v = x; }
     __device__ double get() const { return v; }
     template <typename Real> __device__ Real val() const { return (Real)v; }
-    __device__ void add(float inc) { v += (double)inc; }
     __device__ void add(double inc) { v += inc; }
 };
 template <> struct AccA<true> {

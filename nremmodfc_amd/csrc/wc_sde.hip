@@ -20,7 +20,7 @@
 //     significant bits, both normal over the range that matters) and the three
 //     cross terms hi.hi, hi.lo, lo.hi run on v_mfma_f32_16x16x32_f16 with fp32
 //     accumulation; 1/(2^10 sA) is folded into G.  Same trajectories vs the oracle
-//     as the six-term bf16 split (V_BF16X6, kept as an ablation) at half the MFMAs.
+//     as the six-term bf16 split it replaced, at half the MFMAs (docs/CHANGELOG.md).
 //   fp64 parity path: v_mfma_f64_16x16x4_f64 (rows permuted, Tr<double>).
 // The elementwise update (two logistic sigmoids, homeostatic plasticity,
 // Philox4x32-10 noise + Box-Muller) runs on the VALU beside the MFMAs.
@@ -64,7 +64,7 @@ struct KArgs {
     double* E;
     double* I;
     double* A;
-    const void* frag;  // A-operand image (build_frag / build_frag_bf16)
+    const void* frag;  // A-operand image (build_frag / build_frag_f16)
     void* recE;
     void* recI;
     void* recA;
@@ -85,9 +85,10 @@ struct KArgs {
 };
 
 // ---------------- A-operand (connectome) images ----------------
-// native MFMA: frag[(T*NT + t)*64 + lane][r] = CM[16T + row_node(lane&15)][16t + 4(lane>>4) + r]
+// fp64, native MFMA: frag[(T*NT + t)*64 + lane][r] = CM[16T + row_node(lane&15)][16t + 4(lane>>4) + r]
 template <typename Real, int NT>
 __global__ void build_frag(const double* __restrict__ sc, int N, Real* __restrict__ frag) {
+    static_assert(sizeof(Real) == 8, "the native image is the fp64 path's; fp32 couples through build_frag_f16");
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= NT * NT * 64 * 4) return;
     const int r = idx & 3;
@@ -99,44 +100,18 @@ __global__ void build_frag(const double* __restrict__ sc, int N, Real* __restric
     frag[idx] = (row < N && col < N) ? (Real)sc[(size_t)row * N + col] : (Real)0;
 }
 
-// bf16x6: frag[((T*NC + c)*3 + p)*64 + lane][jj] = part p of
-//   CM[16T + (lane&15)][16(2c + jj/4) + 4(lane>>4) + jj%4]    (k-chunk c = tiles 2c, 2c+1)
-// (the B operand of chunk c, lane l, element jj is E of that same node)
-template <int NT>
-__global__ void build_frag_bf16(const double* __restrict__ sc, int N, bf16x8* __restrict__ frag) {
-    constexpr int NC = NT / 2;
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= NT * NC * 64) return;
-    const int lane = idx & 63;
-    const int tc = idx >> 6;
-    const int T = tc / NC, c = tc % NC;
-    const int row = 16 * T + (lane & 15);
-    bf16x8 part[3];
-#pragma unroll
-    for (int jj = 0; jj < 8; ++jj) {
-        const int col = 16 * (2 * c + (jj >> 2)) + 4 * (lane >> 4) + (jj & 3);
-        const double x = (row < N && col < N) ? sc[(size_t)row * N + col] : 0.0;
-        const __bf16 h = (__bf16)(float)x;
-        const double r1 = x - (double)(float)h;
-        const __bf16 m = (__bf16)(float)r1;
-        part[0][jj] = h;
-        part[1][jj] = m;
-        part[2][jj] = (__bf16)(float)(r1 - (double)(float)m);
-    }
-#pragma unroll
-    for (int p = 0; p < 3; ++p) frag[(size_t)(tc * 3 + p) * 64 + lane] = part[p];
-}
+// the two scale floats follow the two-part fp16 image (inside the fp32 workspace, which frag_bytes
+// sizes larger)
+__host__ __device__ constexpr size_t hf_scale_offset(int NT) { return (size_t)NT * (NT / 2) * 2 * 64 * 16 / 4; }
 
-// the two scale floats follow the fp16 image (inside the fp32 workspace, which is
-// sized for the 3-part bf16 image)
-// (P = 3: the three-part image of V_F16X6; frag_bytes leaves room for the scales behind it)
-__host__ __device__ constexpr size_t hf_scale_offset(int NT, int P = 2) { return (size_t)NT * (NT / 2) * P * 64 * 16 / 4; }
-
-// fp16 x3: frag[((T*NC + c)*2 + p)*64 + lane][jj] = part p of CM[..] sA, hi = fp16(x),
-// lo = fp16(x - hi) (same element order as build_frag_bf16)
+// fp16 x3: frag[((T*NC + c)*2 + p)*64 + lane][jj] = part p of
+//   CM[16T + (lane&15)][16(2c + jj/4) + 4(lane>>4) + jj%4] sA    (k-chunk c = tiles 2c, 2c+1),
+// hi = fp16(x), lo = fp16(x - hi)
+// (the B operand of chunk c, lane l, element jj is E of that same node; P = 2 parts per operand)
 template <int NT, int P = 2>
 __global__ void build_frag_f16(const double* __restrict__ sc, int N, const float* __restrict__ scl,
                                f16x8* __restrict__ frag) {
+    static_assert(P == 2, "two-part operands (hi, lo)");
     constexpr int NC = NT / 2;
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= NT * NC * 64) return;
@@ -153,7 +128,6 @@ __global__ void build_frag_f16(const double* __restrict__ sc, int N, const float
         const double r = x - (double)(float)h;
         part[0][jj] = h;
         part[1][jj] = (_Float16)(float)r;
-        if constexpr (P == 3) part[2][jj] = (_Float16)(float)(r - (double)(float)part[1][jj]);
     }
 #pragma unroll
     for (int p = 0; p < P; ++p) frag[(size_t)(tc * P + p) * 64 + lane] = part[p];
@@ -161,7 +135,7 @@ __global__ void build_frag_f16(const double* __restrict__ sc, int N, const float
 
 // ---------------- packed fp32 cell pair (the fp32 product update) ----------------
 struct PkConsts {
-    f2v a_ee, Pm, knoise, cIe, cIi, cI0, rE, rI, dtE, dtI, dtA, rhoE, cA;
+    f2v a_ee, Pm, knoise, cIe, cIi, cI0, rE, rI, dtE, dtI, dtA, cA;
 };
 
 // V_PKC: the same constants two per VGPR pair (12 registers instead of 26); each use names the
@@ -202,32 +176,24 @@ __device__ __forceinline__ f2v pk_fma_k(f2v ka, f2v b, f2v kc) {
     return d;
 }
 
-// Two cells of the folded-constant fp32 update (wc:77-83; the scalar form is in wc_sde_kernel's
-// kFast branch) as packed fp32 math: v_pk_fma/mul/add_f32 carry two cells per instruction and
-// round exactly like their scalar forms, the transcendentals stay scalar.  Same operations in
-// the same order as the scalar form, so the same bits.
+// Two cells of the folded-constant fp32 update (wc:77-83):
+//   x' = xE - mu; SE = 1/(1 + 2^(x' * (-sigmaE log2 e)));
+//   SI = 1/(1 + 2^(e cIe + in cIi + cI0)); noise = knoise * raw normal
+// as packed fp32 math: v_pk_fma/mul/add_f32 carry two cells per instruction and round exactly
+// like their scalar forms, the transcendentals stay scalar.
 //
-// ES: e is E 2^10 (the units of the MFMA operand split, which then needs no scaling multiply).
-// The host scales a_ee, rE, cIe and dtA by 2^-10 and rhoE by 2^10 (exact), and the sigmoid
+// e is E 2^10 (the units of the MFMA operand split, which then needs no scaling multiply).
+// The host scales a_ee, rE, cIe and dtA by 2^-10 (exact), and the sigmoid
 // returns SE 2^10 as rcp(2^-10 (1 + 2^te)), the denominator by one fma with 2^-10 (exact), so
 // every rounding is the unscaled form's times 2^10: the same trajectory bit for bit (the
 // hardware reciprocal is exponent-transparent; tools/cmp_libs.py checks the bits).
-// WC_INC2 (default): the a_ie increment as in (E dtA - rhoE dtA), two operations instead of
-// three (WC_INC2=0: the round-2 form in (E tA - rhoE tA), tA = in dtA; -2.5% per C3 launch).
-#ifndef WC_F64_PREGS
-#define WC_F64_PREGS 1
-#endif
+// The a_ie increment is in (E dtA - rhoE dtA), two operations (the three-operation form
+// in (E tA - rhoE tA), tA = in dtA, cost 2.5% per C3 launch).
 #ifndef WC_F64_TAB
 #define WC_F64_TAB 0  // 1: the fp64 polynomial coefficients as scalar loads from a laundered table pointer
 #endif
-#ifndef WC_INC2
-#define WC_INC2 1
-#endif
-// LEAN (V_LEAN): a_ie as a two-part running sum without per-step compensation -- lo collects
-// the increments (one add), the value used is hi + lo (one add), and the caller folds lo into
-// hi every 16 steps (renorm_a) -- two operations per cell pair fewer than Kahan-Babuska, the
-// same value to within an fp32 rounding of a_ie.  AII0 (V_AII0): a_ii == 0 (the reference's
-// value, wc:25), so the inhibitory sigmoid's in * cIi term, exactly cI0 + 0, is dropped.
+// AII0 (V_AII0): a_ii == 0 (the reference's value, wc:25), so the inhibitory sigmoid's
+// in * cIi term, exactly cI0 + 0, is dropped.
 #pragma clang fp contract(off)
 // Each constant-carrying operation, in the duplicated (PkConsts) and the two-per-pair (PkB) form
 struct PkOps {
@@ -257,40 +223,29 @@ struct PkOps {
     __device__ static __forceinline__ f2v sti(const PkB& k, f2v d, f2v in0) { return pk_fma_k<1, -1>(k.dt, d, in0); }
 };
 
-template <bool ES = false, bool LEAN = false, bool AII0 = false, typename K = PkConsts>
+template <bool AII0, typename K>
 __device__ __forceinline__ void cell_pair_f32(const K& k, f2v& e, f2v& in, f2v& ahi, f2v& alo, f2v cpl,
                                               f2v G, f2v sl, f2v z) {
     const f2v e0 = e, in0 = in;
     f2v x = PkOps::xe(k, e0);
-    x = __builtin_elementwise_fma(LEAN ? -(ahi + alo) : -ahi, in0, x);
+    x = __builtin_elementwise_fma(-ahi, in0, x);  // (|lo| <= ulp(hi)/2 after every add: hi is the fp32 value)
     x = __builtin_elementwise_fma(G, cpl, x);
     x = PkOps::xz(k, z, x);
     const f2v te = x * sl;
     const f2v ex = {__builtin_amdgcn_exp2f(te.x), __builtin_amdgcn_exp2f(te.y)};
-    const f2v one = {1.0f, 1.0f};
-    constexpr float kS = ES ? 0x1p-10f : 1.0f;
-    const f2v de = ES ? __builtin_elementwise_fma(ex, f2v{kS, kS}, f2v{kS, kS}) : one + ex;
+    constexpr float kS = 0x1p-10f;
+    const f2v de = __builtin_elementwise_fma(ex, f2v{kS, kS}, f2v{kS, kS});
     const f2v SE = {__builtin_amdgcn_rcpf(de.x), __builtin_amdgcn_rcpf(de.y)};
     const f2v ti = PkOps::template ti<AII0>(k, e0, in0);
     const f2v di = 1.0f + f2v{__builtin_amdgcn_exp2f(ti.x), __builtin_amdgcn_exp2f(ti.y)};
     const f2v SI = {__builtin_amdgcn_rcpf(di.x), __builtin_amdgcn_rcpf(di.y)};
     // (a_ie first: e0 and in0 are last read by their own updates, which can then write in place)
-#if WC_INC2
     const f2v inc = in0 * PkOps::inc(k, e0);
-#else
-    static_assert(std::is_same_v<K, PkConsts>, "V_PKC packs the WC_INC2 constants only");
-    const f2v tA = in0 * k.dtA;
-    const f2v inc = __builtin_elementwise_fma(e0, tA, -k.rhoE * tA);
-#endif
-    if constexpr (LEAN) {
-        alo = alo + inc;
-    } else {
-        const f2v t = inc + alo;  // Kahan-Babuska, as AccA<true>::add
-        const f2v s = ahi + t;
-        alo = t - (s - ahi);
-        ahi = s;
-    }
-    // (ES: SE and e0 both carry 2^10, rE 2^-10: the same roundings times 2^10)
+    const f2v t = inc + alo;  // Kahan-Babuska, as AccA<true>::add
+    const f2v s = ahi + t;
+    alo = t - (s - ahi);
+    ahi = s;
+    // (SE and e0 both carry 2^10, rE 2^-10: the same roundings times 2^10)
     e = PkOps::ste(k, __builtin_elementwise_fma(PkOps::re(k, e0), SE, -e0), e0);
     in = PkOps::sti(k, __builtin_elementwise_fma(PkOps::ri(k, in0), SI, -in0), in0);
 }
@@ -298,30 +253,22 @@ __device__ __forceinline__ void cell_pair_f32(const K& k, f2v& e, f2v& in, f2v& 
 #pragma clang fp contract(on)
 
 // ---------------- variants ----------------
+// (the values are part of the kernels' symbol names; the gaps are retired experiments, docs/CHANGELOG.md)
 enum : int {
-    V_FRAG_REGS = 1,  // A-operand fragments held in registers (else streamed from LDS each step)
+    V_FRAG_REGS = 1,  // fp32: A-operand fragments held in registers (else streamed from LDS each step)
     V_NO_RNG = 2,     // ablation: noise term zero
     V_NO_MFMA = 4,    // ablation: coupling skipped
-    V_KAHAN_A = 8,    // fp32: a_ie as a compensated fp32 pair instead of fp64
-    V_BF16X6 = 32,    // fp32 coupling as the six bf16 cross terms (product)
-    V_BF16X3 = 64,    // ablation: only the three leading terms (~2^-17 relative)
+    V_KAHAN_A = 8,    // fp32: a_ie as a compensated fp32 pair (set in every fp32 kernel)
     V_REC2 = 128,     // node-major E records buffered 2 deep: one 8-B store per node per 2 records
-    V_REC4 = 256,     // ... 4 deep: one 16-B store per node per 4 records (host checks eligibility)
-    V_F16X3 = 512,    // fp32 coupling as three fp16 cross terms of two-part (22-bit) operands
-    V_ZFIRST = 1024,  // fp32 fast path: the step's normals drawn before the coupling MFMAs
-    V_ILV = 2048,     // ... interleaved with them (sched_group_barrier: 1 MFMA, 6 VALU)
-    V_ILV2 = 4096,    // ... interleaved with them (1 MFMA, 2 VALU: the free half of a 16x16x32 gap)
-    V_SCALAR = 8192,  // ablation: the fp32 fast update one cell per instruction (round-2 form)
+    V_F16X3 = 512,    // fp32 coupling as three fp16 cross terms of two-part (22-bit) operands (set in every
+                      // fp32 kernel)
     V_MIX = 16384,    // NT = 6 over NW = 4 waves per group, two waves with 2 tiles and two with 1,
                       // the pattern rotated per group so the SIMDs of a 3-group workgroup carry
                       // 5/4/5/4 tiles instead of 6/4/4/4 (3 waves of 2 tiles)
-    V_LEAN = 32768,   // packed fp32 update: a_ie as hi + lo running sum, renormalised every 16 steps
     V_AII0 = 65536,   // a_ii == 0 (host-checked): the inhibitory sigmoid without its in * cIi term
     V_ZMEM = 131072,  // the raw normals come precomputed from zbuf (zblock_kernel on otherwise idle CUs)
     V_HALF2 = 262144, // NW = 2 NT: two waves per node tile, each updating two of a lane's four rows
                       // (both run the tile's coupling MFMAs; with V_ZMEM, so no Philox is repeated)
-    V_F16X6 = 1048576, // A/B: three-part fp16 operands (E and CM each hi + mid + lo), six cross terms
-                       // down to 2^-22 (>= 24 significant bits of both operands)
     V_ZPAIR = 524288, // SG = 2, V_ZMEM, one workgroup per CU: workgroups < zgen_b0 integrate two groups,
                       // the others one group while their second group's waves draw the next block's
                       // normals, one step's share per step between the workgroup's barriers
@@ -332,58 +279,53 @@ enum : int {
                       // waves of its SIMD read LDS and run MFMAs (the same operations per cell: the same bits)
 };
 
-constexpr bool kFragRegs_(int var) { return (var & V_FRAG_REGS) != 0; }
-
 // SG > 1: one workgroup holds SG groups of 16 simulations (SG x NW waves) that
 // share ONE LDS copy of the connectome image; each group has its own E exchange.
+//
+// Two arithmetic configurations, chosen by Real:
+//   float:  fp16 x3 coupling (V_F16X3), a_ie as a compensated fp32 pair (V_KAHAN_A), the packed
+//           folded-constant update cell_pair_f32 with E held in units of 2^-10 (E[][] is E 2^10, so
+//           the MFMA operand split needs no scaling multiply) and Sl holding -sigmaE log2 e;
+//   double: native fp64 MFMAs on an LDS image, fp64 a_ie, the unfolded update.
 template <typename Real, int NT, int NW, int VAR, int MINW, int SG = 1>
 __global__ void __launch_bounds__(NW * 64 * SG, MINW) wc_sde_kernel(const KArgs a) {
     typedef typename Tr<Real>::acc_t acc_t;
     typedef __attribute__((ext_vector_type(4))) Real real4;
+    // The fp16 operand parts are held and moved as opaque 16- and 8-byte dword vectors and cast to f16x8
+    // only at the MFMA: no arithmetic is done on them, and with an fp16 element type the compiler's vector
+    // combines change the register allocation of the four- and five-group kernels (126 -> 130 VGPRs,
+    // 12 bytes of scratch in the C3 one).
+    typedef uint32_t raw8 __attribute__((ext_vector_type(4)));  // eight fp16: one part of a 32-node chunk
+    typedef uint32_t raw4 __attribute__((ext_vector_type(2)));  // four fp16: one tile's share of it
+    constexpr bool kF32 = sizeof(Real) == 4;
+    constexpr int kAblate = V_NO_RNG | V_NO_MFMA;
+    static_assert(kF32 ? (VAR & V_F16X3) != 0 && (VAR & V_KAHAN_A) != 0 && NT % 2 == 0 : (VAR & ~kAblate) == 0,
+                  "fp32: fp16 x3 coupling (even tile count) with the compensated a_ie; fp64: ablation bits only");
     constexpr bool kMix = (VAR & V_MIX) != 0;
     constexpr bool kHalf = (VAR & V_HALF2) != 0;
     static_assert(kMix ? (NT == 6 && NW == 4) : kHalf ? (NW == 2 * NT && SG == 1) : NT % NW == 0, "NW must divide NT");
     constexpr int OT = kMix ? 2 : kHalf ? 1 : NT / NW;  // tile slots per wave
     constexpr int RW = kHalf ? 2 : 4;                    // rows of a lane's 4 (one MFMA column quad) owned
-    constexpr bool kHf3 = (VAR & V_F16X6) != 0;
-    constexpr bool kHf = (VAR & (V_F16X3 | V_F16X6)) != 0;
-    constexpr int kTerms = (VAR & V_BF16X6) ? 6 : (VAR & V_BF16X3) ? 3 : kHf3 ? 6 : kHf ? 3 : 0;
-    constexpr bool kBf = kTerms > 0;  // 16-bit split coupling (bf16 or fp16 parts)
-    static_assert(!kBf || (sizeof(Real) == 4 && NT % 2 == 0), "split coupling: fp32, even tile count");
-    constexpr int NC = NT / 2;  // 16-bit k-chunks (2 tiles = 32 nodes)
-    constexpr int NP = kTerms == 6 ? 3 : 2;
-    constexpr int PS = (kHf && !kHf3) ? 2 : 3;  // parts per chunk in the images
+    constexpr int NC = NT / 2;  // fp16 k-chunks (2 tiles = 32 nodes)
+    constexpr int NP = 2;       // fp16 parts per operand (hi, lo)
     constexpr bool kFragRegs = (VAR & V_FRAG_REGS) != 0;
     constexpr bool kRng = (VAR & V_NO_RNG) == 0;
     constexpr bool kMfma = (VAR & V_NO_MFMA) == 0;
-    constexpr bool kPairA = sizeof(Real) == 4 && (VAR & V_KAHAN_A) != 0;
-    // G and the slope per cell in registers (fp64: WC_F64_PREGS; else re-read from memory every step)
-    constexpr bool kParamRegs = sizeof(Real) == 4 || WC_F64_PREGS;
-    // fp32 with the compensated a_ie: the folded-constant update (Sl holds -sigmaE log2 e)
-    constexpr bool kFast = sizeof(Real) == 4 && kPairA;
-    constexpr bool kZFirst = kFast && kRng && (VAR & V_ZFIRST) != 0;
-    constexpr bool kPk = (VAR & V_SCALAR) == 0;  // packed fp32 cell pairs (cell_pair_f32)
-    // the fp16x3 packed product path keeps E in units of 2^-10 (E[][] holds E 2^10): the
-    // MFMA operand split needs no scaling multiply (cell_pair_f32<true>)
-    constexpr bool kEs = kFast && kPk && kHf;
-    constexpr bool kLean = kFast && kPk && (VAR & V_LEAN) != 0;
-    constexpr bool kAii0 = kFast && kPk && (VAR & V_AII0) != 0;
-    constexpr bool kZMem = kFast && kPk && kRng && (VAR & V_ZMEM) != 0;
-    static_assert(!kHalf || (kZMem && kHf && !kHf3), "V_HALF2: the fp16x3 packed path with precomputed normals");
+    constexpr bool kAii0 = (VAR & V_AII0) != 0;
+    constexpr bool kZMem = (VAR & V_ZMEM) != 0;
+    static_assert(!kZMem || kRng, "V_ZMEM: the normals are read, not switched off");
+    static_assert(!kHalf || kZMem, "V_HALF2: precomputed normals");
     constexpr bool kZPair = (VAR & V_ZPAIR) != 0;
     static_assert(!kZPair || (kZMem && SG == 2 && NW > 1 && !kHalf), "V_ZPAIR: two groups, normals from zbuf");
     constexpr bool kPkc = (VAR & V_PKC) != 0;
-    static_assert(!kPkc || (kFast && kPk), "V_PKC: the packed fp32 update");
     constexpr bool kStag = (VAR & V_STAG) != 0;
-    static_assert(!kStag || (kFast && kPk && kRng && !kZMem && !kZFirst && !kMix && NW > 1),
-                  "V_STAG: the packed fp32 update drawing its own normals, several waves per workgroup");
-    constexpr float kEsc = kEs ? 1024.0f : 1.0f, kEinv = kEs ? 0x1p-10f : 1.0f;
-    // VALU slots after each MFMA in the interleaved schedule (0: compiler's own order)
-    constexpr int kIlv = !(kZFirst && kBf && kMfma) ? 0 : (VAR & V_ILV) ? 6 : (VAR & V_ILV2) ? 2 : 0;
-    constexpr int kFragUnits = kBf ? NT * NC * PS : NT * NT;  // 16-B (bf16x8 / real4 f32) or 32-B units
+    static_assert(!kStag || (kRng && !kZMem && !kMix && NW > 1),
+                  "V_STAG: a kernel drawing its own normals, several waves per workgroup");
+    constexpr float kEsc = kF32 ? 1024.0f : 1.0f, kEinv = kF32 ? 0x1p-10f : 1.0f;
+    constexpr int kFragUnits = kF32 ? NT * NC * NP : NT * NT;  // 16-B (raw8) or 32-B (fp64 real4) units
 
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    if constexpr ((VAR & V_ZMEM) != 0 && !kZPair) {
+    if constexpr (kZMem && !kZPair) {
         if ((int)blockIdx.x >= a.zgen_b0) {  // generator workgroup: the next block's normals, grid-stride
             const uint32_t total = (uint32_t)a.zgen_K * NT * (uint32_t)a.zBp * 4u;
             const uint32_t stride = (gridDim.x - a.zgen_b0) * blockDim.x;
@@ -398,11 +340,11 @@ __global__ void __launch_bounds__(NW * 64 * SG, MINW) wc_sde_kernel(const KArgs 
         }
     }
     // LDS: [A-operand image, unless kFragRegs] [E exchange, 2 buffers, if NW > 1]
-    const size_t frag_bytes = kFragRegs ? 0 : (size_t)kFragUnits * 64 * (kBf ? 16 : sizeof(real4));
+    const size_t frag_bytes = kFragRegs ? 0 : (size_t)kFragUnits * 64 * (kF32 ? 16 : sizeof(real4));
     const int grp = SG == 1 ? 0 : (threadIdx.x >> 6) / NW;
     char* xraw = smem + frag_bytes;
-    bf16x8* xb16 = reinterpret_cast<bf16x8*>(xraw) + grp * (2 * NC * PS * 64);  // [2][NC][PS][64] per group
-    real4* xbn = reinterpret_cast<real4*>(xraw) + grp * (2 * NT * 64);         // [2][NT][64] per group
+    raw8* xb16 = reinterpret_cast<raw8*>(xraw) + grp * (2 * NC * NP * 64);  // fp32: [2][NC][NP][64] per group
+    real4* xbn = reinterpret_cast<real4*>(xraw) + grp * (2 * NT * 64);       // fp64: [2][NT][64] per group
 
     const int lane = threadIdx.x & 63;
     const int w = SG == 1 ? threadIdx.x >> 6 : (threadIdx.x >> 6) % NW;
@@ -421,7 +363,7 @@ __global__ void __launch_bounds__(NW * 64 * SG, MINW) wc_sde_kernel(const KArgs 
     int T0 = NW == 1 ? 0 : kHalf ? (w >> 1) : w * OT, nt = OT;
     const int R0 = kHalf ? 2 * (w & 1) : 0;  // first owned row of the lane's four
     if constexpr (kMix) {
-        static_assert(!kFragRegs_(VAR) && (VAR & V_ZFIRST) == 0, "V_MIX: LDS fragments, plain schedule");
+        static_assert(!kFragRegs, "V_MIX: LDS fragments");
         const int rot = grp & 3;
         auto cnt = [&](int v) { return ((v + 4 - rot) & 3) < 2 ? 2 : 1; };  // (2, 2, 1, 1) rotated
         nt = cnt(w);
@@ -432,26 +374,20 @@ __global__ void __launch_bounds__(NW * 64 * SG, MINW) wc_sde_kernel(const KArgs 
     auto owned = [&](int u) { return !kMix || u < nt; };  // (wave-uniform)
 
     // ---- A operand: this wave's rows, in registers or the whole image in LDS ----
-    constexpr bool kRegBf = kFragRegs && kBf, kRegN = kFragRegs && !kBf;
-    bf16x8 F16[kRegBf ? OT : 1][kRegBf ? NC : 1][kRegBf ? NP : 1];
-    real4 FN[kRegN ? OT : 1][kRegN ? NT : 1];
+    static_assert(!kFragRegs || kF32, "V_FRAG_REGS: the fp16 image (the fp64 image is streamed from LDS)");
+    raw8 F16[kFragRegs ? OT : 1][kFragRegs ? NC : 1][kFragRegs ? NP : 1];
     {
-        const bf16x8* g16 = reinterpret_cast<const bf16x8*>(a.frag);
+        const raw8* g16 = reinterpret_cast<const raw8*>(a.frag);
         const real4* gn = reinterpret_cast<const real4*>(a.frag);
-        if constexpr (kRegBf) {
+        if constexpr (kFragRegs) {
 #pragma unroll
             for (int u = 0; u < OT; ++u)
 #pragma unroll
                 for (int c = 0; c < NC; ++c)
 #pragma unroll
-                    for (int p = 0; p < NP; ++p) F16[u][c][p] = g16[((TL(u) * NC + c) * PS + p) * 64 + lane];
-        } else if constexpr (kRegN) {
-#pragma unroll
-            for (int u = 0; u < OT; ++u)
-#pragma unroll
-                for (int t = 0; t < NT; ++t) FN[u][t] = gn[(TL(u) * NT + t) * 64 + lane];
-        } else if constexpr (kBf) {
-            bf16x8* l16 = reinterpret_cast<bf16x8*>(smem);
+                    for (int p = 0; p < NP; ++p) F16[u][c][p] = g16[((TL(u) * NC + c) * NP + p) * 64 + lane];
+        } else if constexpr (kF32) {
+            raw8* l16 = reinterpret_cast<raw8*>(smem);
             for (int i = threadIdx.x; i < kFragUnits * 64; i += blockDim.x) l16[i] = g16[i];
         } else {
             real4* ln = reinterpret_cast<real4*>(smem);
@@ -462,12 +398,12 @@ __global__ void __launch_bounds__(NW * 64 * SG, MINW) wc_sde_kernel(const KArgs 
     const uint64_t key = a.keys[bb];
     // fp16 coupling: the MFMA sums CM sA x E 2^10; 1 / (2^10 sA) is folded into G (exact)
     Real gscale = 1;
-    if constexpr (kHf) gscale = reinterpret_cast<const float*>(a.frag)[hf_scale_offset(NT, PS) + 1];
+    if constexpr (kF32) gscale = reinterpret_cast<const float*>(a.frag)[hf_scale_offset(NT) + 1];
 
-    // ---- own state and per-node parameters ----
-    constexpr int PT = kParamRegs ? OT : 1;
-    Real E[OT][RW], I[OT][RW], Gc[PT][RW], Sl[PT][RW];
-    AccA<kPairA> A[OT][RW];
+    // ---- own state and per-node parameters (G and the slope per cell stay in registers in fp64 too:
+    // re-read from memory every step, a C3 launch took 356.2 instead of 329.5 ms) ----
+    Real E[OT][RW], I[OT][RW], Gc[OT][RW], Sl[OT][RW];
+    AccA<kF32> A[OT][RW];
 #pragma unroll
     for (int u = 0; u < OT; ++u)
 #pragma unroll
@@ -478,39 +414,26 @@ __global__ void __launch_bounds__(NW * 64 * SG, MINW) wc_sde_kernel(const KArgs 
             E[u][r] = ok ? (Real)a.E[o] * (Real)kEsc : (Real)0;
             I[u][r] = ok ? (Real)a.I[o] : (Real)0;
             A[u][r].set(ok ? a.A[o] : 0.0);
-            if constexpr (kParamRegs) {
-                Gc[u][r] = ok ? (Real)a.G[o] * gscale : (Real)0;
-                Sl[u][r] = ok ? (kFast ? -1 : 1) * Tr<Real>::slope(a.sigmaE[o]) : (Real)0;
-            }
+            Gc[u][r] = ok ? (Real)a.G[o] * gscale : (Real)0;
+            Sl[u][r] = ok ? (kF32 ? -1 : 1) * Tr<Real>::slope(a.sigmaE[o]) : (Real)0;
         }
 
     // ---- B operand (E of every node) ----
     // NW == 1: registers.  NW > 1: each wave publishes its own tiles to the LDS
     // image of the step, then every wave reads chunks back at the point of use
     // (register arrays are only ever indexed by compile-time constants).
-    bf16x8 XB[(kBf && NW == 1) ? NC : 1][NP];
-    Real X[(!kBf && NW == 1) ? NT : 1][4];
+    raw8 XB[(kF32 && NW == 1) ? NC : 1][NP];
+    Real X[(!kF32 && NW == 1) ? NT : 1][4];
     auto publish = [&](int buf) {
         if constexpr (NW == 1) {
-            if constexpr (kBf) {
+            if constexpr (kF32) {
 #pragma unroll
                 for (int c = 0; c < NC; ++c) {
-                    bf16x4 h0, m0, l0, h1, m1, l1;
-                    if constexpr (kHf3) {
-                        split3h<kEs>(E[2 * c], reinterpret_cast<f16x4&>(h0), reinterpret_cast<f16x4&>(m0),
-                                     reinterpret_cast<f16x4&>(l0));
-                        split3h<kEs>(E[2 * c + 1], reinterpret_cast<f16x4&>(h1), reinterpret_cast<f16x4&>(m1),
-                                     reinterpret_cast<f16x4&>(l1));
-                    } else if constexpr (kHf) {
-                        split2h<kEs>(E[2 * c], reinterpret_cast<f16x4&>(h0), reinterpret_cast<f16x4&>(m0));
-                        split2h<kEs>(E[2 * c + 1], reinterpret_cast<f16x4&>(h1), reinterpret_cast<f16x4&>(m1));
-                    } else {
-                        split3(E[2 * c], h0, m0, l0);
-                        split3(E[2 * c + 1], h1, m1, l1);
-                    }
-                    XB[c][0] = __builtin_shufflevector(h0, h1, 0, 1, 2, 3, 4, 5, 6, 7);
-                    XB[c][1] = __builtin_shufflevector(m0, m1, 0, 1, 2, 3, 4, 5, 6, 7);
-                    if constexpr (NP == 3) XB[c][2] = __builtin_shufflevector(l0, l1, 0, 1, 2, 3, 4, 5, 6, 7);
+                    raw4 h0, l0, h1, l1;
+                    split2h<true>(E[2 * c], reinterpret_cast<f16x4&>(h0), reinterpret_cast<f16x4&>(l0));
+                    split2h<true>(E[2 * c + 1], reinterpret_cast<f16x4&>(h1), reinterpret_cast<f16x4&>(l1));
+                    XB[c][0] = __builtin_shufflevector(h0, h1, 0, 1, 2, 3);
+                    XB[c][1] = __builtin_shufflevector(l0, l1, 0, 1, 2, 3);
                 }
             } else {
 #pragma unroll
@@ -521,26 +444,22 @@ __global__ void __launch_bounds__(NW * 64 * SG, MINW) wc_sde_kernel(const KArgs 
         } else {
             if constexpr (kHalf) {
                 // the owned two rows: one dword (two fp16) of the tile's 8-B slot per part
-                uint32_t* x2 = reinterpret_cast<uint32_t*>(xb16 + buf * NC * PS * 64);
+                uint32_t* x2 = reinterpret_cast<uint32_t*>(xb16 + buf * NC * NP * 64);
                 const int t = TL(0);
                 uint32_t hl[2];
-                split2h_pair<kEs>(E[0], hl[0], hl[1]);
+                split2h_pair<true>(E[0], hl[0], hl[1]);
 #pragma unroll
-                for (int p = 0; p < 2; ++p) x2[((((t >> 1) * PS + p) * 64 + lane) * 2 + (t & 1)) * 2 + (R0 >> 1)] = hl[p];
-            } else if constexpr (kBf) {
-                bf16x4* x4 = reinterpret_cast<bf16x4*>(xb16 + buf * NC * PS * 64);
+                for (int p = 0; p < NP; ++p) x2[((((t >> 1) * NP + p) * 64 + lane) * 2 + (t & 1)) * 2 + (R0 >> 1)] = hl[p];
+            } else if constexpr (kF32) {
+                raw4* x4 = reinterpret_cast<raw4*>(xb16 + buf * NC * NP * 64);
 #pragma unroll
                 for (int u = 0; u < OT; ++u) {
                     if (!owned(u)) continue;
                     const int t = TL(u);  // chunk t/2, half t&1 (runtime: address arithmetic only)
-                    bf16x4 hmo[3];
-                    if constexpr (kHf3)
-                        split3h<kEs>(E[u], reinterpret_cast<f16x4&>(hmo[0]), reinterpret_cast<f16x4&>(hmo[1]),
-                                     reinterpret_cast<f16x4&>(hmo[2]));
-                    else if constexpr (kHf) split2h<kEs>(E[u], reinterpret_cast<f16x4&>(hmo[0]), reinterpret_cast<f16x4&>(hmo[1]));
-                    else split3(E[u], hmo[0], hmo[1], hmo[2]);
+                    raw4 hl[NP];
+                    split2h<true>(E[u], reinterpret_cast<f16x4&>(hl[0]), reinterpret_cast<f16x4&>(hl[1]));
 #pragma unroll
-                    for (int p = 0; p < NP; ++p) x4[(((t >> 1) * PS + p) * 64 + lane) * 2 + (t & 1)] = hmo[p];
+                    for (int p = 0; p < NP; ++p) x4[(((t >> 1) * NP + p) * 64 + lane) * 2 + (t & 1)] = hl[p];
                 }
             } else {
                 real4* xb = xbn + buf * NT * 64;
@@ -599,7 +518,7 @@ __global__ void __launch_bounds__(NW * 64 * SG, MINW) wc_sde_kernel(const KArgs 
     Real a_ee = (Real)a.a_ee, a_ei = (Real)a.a_ei, a_ii = (Real)a.a_ii;
     Real P = (Real)a.P, rhoE = (Real)a.rhoE, rE = (Real)a.rE, rI = (Real)a.rI;
     Real mu = (Real)a.mu, slI = Tr<Real>::slope(a.sigmaI), sqdtD = (Real)a.sqdtD;
-    // fp32 product path: folded constants (see the kFast update)
+    // fp32: folded constants (see cell_pair_f32)
     const float Pm = (float)(a.P - a.mu), knoise = (float)(a.sqdtD * (double)kSqrt2Ln2);
     const float cIe = (float)(-a.a_ei * a.sigmaI * 1.4426950408889634);
     const float cIi = (float)(a.a_ii * a.sigmaI * 1.4426950408889634);
@@ -621,16 +540,17 @@ __global__ void __launch_bounds__(NW * 64 * SG, MINW) wc_sde_kernel(const KArgs 
     PkConsts pkd{};
     PkB pkb{};
     if constexpr (kPkc) {
-        // (-rE, -rI negated here; kEs scalings as below)
+        static_assert(kF32, "V_PKC: the packed fp32 update");
+        // (-rE, -rI negated here; 2^-10 scalings as below)
         pkb = PkB{f2v{(float)a_ee * kEinv, Pm}, f2v{cIe * kEinv, cI0}, f2v{knoise, cIi},
                   f2v{-((float)rE * kEinv), -(float)rI}, f2v{(float)dtE, (float)dtI},
                   f2v{(float)dtA * kEinv, (float)(-a.rhoE * a.dtSim / a.tau_ip)}};
-    } else if constexpr (kFast && kPk) {
+    } else if constexpr (kF32) {
         auto bc = [](float v) { return f2v{v, v}; };
-        // (kEs: E-side constants carry 2^-10, rhoE 2^10, all exact)
+        // (E-side constants carry 2^-10, exact)
         pkd = PkConsts{bc((float)a_ee * kEinv), bc(Pm), bc(knoise), bc(cIe * kEinv), bc(cIi), bc(cI0),
                        bc((float)rE * kEinv), bc((float)rI), bc((float)dtE), bc((float)dtI),
-                       bc((float)dtA * kEinv), bc((float)rhoE * kEsc), bc((float)(-a.rhoE * a.dtSim / a.tau_ip))};
+                       bc((float)dtA * kEinv), bc((float)(-a.rhoE * a.dtSim / a.tau_ip))};
     }
     const auto& pk = *[&] {
         if constexpr (kPkc) return &pkb;
@@ -640,7 +560,7 @@ __global__ void __launch_bounds__(NW * 64 * SG, MINW) wc_sde_kernel(const KArgs 
     const int rec_every = (int)a.rec_every;
     int rec_cnt = 0, rec_row = 0;
     // record buffer (RB > 1): the RB-1 previous E records of this lane's nodes, oldest first
-    constexpr int RB = (VAR & V_REC4) ? 4 : (VAR & V_REC2) ? 2 : 1;
+    constexpr int RB = (VAR & V_REC2) ? 2 : 1;
     Real rbuf[RB > 1 ? OT : 1][RW][RB > 1 ? RB - 1 : 1];
 
     // V_ZMEM: normals of the next kZD steps in flight
@@ -674,6 +594,7 @@ __global__ void __launch_bounds__(NW * 64 * SG, MINW) wc_sde_kernel(const KArgs 
             if (rec_cnt == 0) {
                 if constexpr (RB > 1) {
                     // node-major ring, E only: flush RB records as one vector store per node
+                    static_assert(RB == 2, "one 8-B store per node per two records");
                     if (rec_row % RB == RB - 1) {
                         if (live) {
 #pragma unroll
@@ -684,13 +605,8 @@ __global__ void __launch_bounds__(NW * 64 * SG, MINW) wc_sde_kernel(const KArgs 
                                     if (n < N) {
                                         Real* dst = static_cast<Real*>(a.recE) + ((size_t)bb * N + n) * a.rec_ld +
                                                     (rec_row - (RB - 1));
-                                        if constexpr (RB == 4) {
-                                            *reinterpret_cast<real4*>(dst) =
-                                                real4{rbuf[u][r][0], rbuf[u][r][1], rbuf[u][r][2], E[u][r] * (Real)kEinv};
-                                        } else {
-                                            typedef __attribute__((ext_vector_type(2))) Real real2;
-                                            *reinterpret_cast<real2*>(dst) = real2{rbuf[u][r][0], E[u][r] * (Real)kEinv};
-                                        }
+                                        typedef __attribute__((ext_vector_type(2))) Real real2;
+                                        *reinterpret_cast<real2*>(dst) = real2{rbuf[u][r][0], E[u][r] * (Real)kEinv};
                                     }
                                 }
                         }
@@ -771,12 +687,6 @@ __global__ void __launch_bounds__(NW * 64 * SG, MINW) wc_sde_kernel(const KArgs 
                 zq[ZS][u] = zload(sl, u);
             }
         }
-        // V_ZFIRST: the normals do not depend on the coupling, so they can fill the MFMA chain's gaps
-        float zz[kZFirst ? OT : 1][4];
-        if constexpr (kZFirst) {
-#pragma unroll
-            for (int u = 0; u < OT; ++u) quad_normals_raw(gstep, (uint32_t)(4 * TL(u) + g), key, zz[u]);
-        }
         // V_STAG, role B: the update's own calls with the same arguments, issued while the role-A
         // waves of this SIMD are in their coupling phase
         f2v zh[kStag ? OT : 1][2];
@@ -786,47 +696,30 @@ __global__ void __launch_bounds__(NW * 64 * SG, MINW) wc_sde_kernel(const KArgs 
                 for (int u = 0; u < OT; ++u) quad_normals_pk(gstep, (uint32_t)(4 * TL(u) + g), key, zh[u]);
             }
         }
-        if constexpr (kMfma && kBf) {
-            const bf16x8* l16 = reinterpret_cast<const bf16x8*>(smem);
-            const bf16x8* xb = xb16 + buf * NC * PS * 64;
+        if constexpr (kMfma && kF32) {
+            const raw8* l16 = reinterpret_cast<const raw8*>(smem);
+            const raw8* xb = xb16 + buf * NC * NP * 64;
 #pragma unroll
             for (int c = 0; c < NC; ++c) {
-                bf16x8 xe[NP];
+                raw8 xe[NP];
 #pragma unroll
                 for (int p = 0; p < NP; ++p) {
                     if constexpr (NW == 1) xe[p] = XB[c][p];
-                    else xe[p] = xb[(c * PS + p) * 64 + fl];
+                    else xe[p] = xb[(c * NP + p) * 64 + fl];
                 }
 #pragma unroll
                 for (int u = 0; u < OT; ++u) {
                     if (!owned(u)) continue;
-                    bf16x8 f[NP];
+                    raw8 f[NP];
 #pragma unroll
                     for (int p = 0; p < NP; ++p) {
                         if constexpr (kFragRegs) f[p] = F16[u][c][p];
-                        else f[p] = l16[((TL(u) * NC + c) * PS + p) * 64 + fl];
+                        else f[p] = l16[((TL(u) * NC + c) * NP + p) * 64 + fl];
                     }
-                    if constexpr (kHf) {  // small terms first: [2^-22 (lo.hi, mid.mid, hi.lo)], 2^-11 (lo.hi, hi.lo), 1 (hi.hi)
-                        typedef f16x8 h8;
-                        if constexpr (kHf3) {
-                            acc[u] = __builtin_amdgcn_mfma_f32_16x16x32_f16((h8)f[2], (h8)xe[0], acc[u], 0, 0, 0);
-                            acc[u] = __builtin_amdgcn_mfma_f32_16x16x32_f16((h8)f[1], (h8)xe[1], acc[u], 0, 0, 0);
-                            acc[u] = __builtin_amdgcn_mfma_f32_16x16x32_f16((h8)f[0], (h8)xe[2], acc[u], 0, 0, 0);
-                        }
-                        acc[u] = __builtin_amdgcn_mfma_f32_16x16x32_f16((h8)f[1], (h8)xe[0], acc[u], 0, 0, 0);
-                        acc[u] = __builtin_amdgcn_mfma_f32_16x16x32_f16((h8)f[0], (h8)xe[1], acc[u], 0, 0, 0);
-                        acc[u] = __builtin_amdgcn_mfma_f32_16x16x32_f16((h8)f[0], (h8)xe[0], acc[u], 0, 0, 0);
-                        continue;
-                    }
-                    // small terms first: 2^-18 (lo.hi, mid.mid, hi.lo), 2^-9 (mid.hi, hi.mid), 1 (hi.hi)
-                    if constexpr (NP == 3) {
-                        acc[u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f[2], xe[0], acc[u], 0, 0, 0);
-                        acc[u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f[1], xe[1], acc[u], 0, 0, 0);
-                        acc[u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f[0], xe[2], acc[u], 0, 0, 0);
-                    }
-                    acc[u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f[1], xe[0], acc[u], 0, 0, 0);
-                    acc[u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f[0], xe[1], acc[u], 0, 0, 0);
-                    acc[u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f[0], xe[0], acc[u], 0, 0, 0);
+                    // small terms first: 2^-11 (lo.hi, hi.lo), 1 (hi.hi)
+                    acc[u] = __builtin_amdgcn_mfma_f32_16x16x32_f16((f16x8)f[1], (f16x8)xe[0], acc[u], 0, 0, 0);
+                    acc[u] = __builtin_amdgcn_mfma_f32_16x16x32_f16((f16x8)f[0], (f16x8)xe[1], acc[u], 0, 0, 0);
+                    acc[u] = __builtin_amdgcn_mfma_f32_16x16x32_f16((f16x8)f[0], (f16x8)xe[0], acc[u], 0, 0, 0);
                 }
             }
         } else if constexpr (kMfma) {
@@ -845,25 +738,14 @@ __global__ void __launch_bounds__(NW * 64 * SG, MINW) wc_sde_kernel(const KArgs 
                 }
 #pragma unroll
                 for (int u = 0; u < OT; ++u) {
-                    if constexpr (!kFragRegs && sizeof(Real) == 8)
-                        if ((u & 1) == 0) __builtin_amdgcn_sched_barrier(0);  // bound fp64 read look-ahead
-                    const real4 f = kFragRegs ? FN[u][t] : ln[(TL(u) * NT + t) * 64 + fl];
+                    if ((u & 1) == 0) __builtin_amdgcn_sched_barrier(0);  // bound fp64 read look-ahead
+                    const real4 f = ln[(TL(u) * NT + t) * 64 + fl];
 #pragma unroll
                     for (int r = 0; r < 4; ++r) acc[u] = Tr<Real>::mfma(f[r], xe[r], acc[u]);
                 }
             }
         }
 
-        if constexpr (kIlv > 0) {
-            // LDS reads first, then each MFMA followed by a slice of the (independent) normal generation
-#pragma unroll
-            for (int i = 0; i < NC * NP * (OT + 1); ++i) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-#pragma unroll
-            for (int i = 0; i < NC * OT * kTerms; ++i) {
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(0x002, kIlv, 0);
-            }
-        }
         // V_STAG, role A: the same draws here, after the coupling, for all its tiles at once
         // (independent Philox chains side by side, as in role B)
         if constexpr (kStag) {
@@ -876,15 +758,13 @@ __global__ void __launch_bounds__(NW * 64 * SG, MINW) wc_sde_kernel(const KArgs 
 #pragma unroll
         for (int u = 0; u < OT; ++u) {
             if (!owned(u)) continue;
-            if constexpr (sizeof(Real) == 8) __builtin_amdgcn_sched_barrier(0);  // fp64: bound live ranges
-            Real z[4] = {0, 0, 0, 0};
             if constexpr (kHalf) {
                 // the owned pair (rows R0, R0 + 1): pair R0 / 2 of the full-tile form, same operations
                 f2v e = {E[u][0], E[u][1]}, in = {I[u][0], I[u][1]};
                 f2v ahi = {A[u][0].hi, A[u][1].hi}, alo = {A[u][0].lo, A[u][1].lo};
                 const f2v cpl = R0 ? f2v{acc[u][2], acc[u][3]} : f2v{acc[u][0], acc[u][1]};
-                cell_pair_f32<kEs, kLean, kAii0>(pk, e, in, ahi, alo, cpl, f2v{Gc[u][0], Gc[u][1]},
-                                                  f2v{Sl[u][0], Sl[u][1]}, f2v{zm[u].x, zm[u].y});
+                cell_pair_f32<kAii0>(pk, e, in, ahi, alo, cpl, f2v{Gc[u][0], Gc[u][1]}, f2v{Sl[u][0], Sl[u][1]},
+                                     f2v{zm[u].x, zm[u].y});
                 E[u][0] = e.x;
                 E[u][1] = e.y;
                 I[u][0] = in.x;
@@ -893,15 +773,14 @@ __global__ void __launch_bounds__(NW * 64 * SG, MINW) wc_sde_kernel(const KArgs 
                 A[u][1].hi = ahi.y;
                 A[u][0].lo = alo.x;
                 A[u][1].lo = alo.y;
-                continue;
-            } else if constexpr (kFast && kPk) {
+            } else if constexpr (kF32) {
                 f2v zp[2] = {f2v{0, 0}, f2v{0, 0}};
                 if constexpr (kZMem) {
                     zp[0] = f2v{zm[u].x, zm[u].y};
                     zp[1] = f2v{zm[u].z, zm[u].w};
-                } else if constexpr (kZFirst) {
-                    zp[0] = f2v{zz[u][0], zz[u][1]};
-                    zp[1] = f2v{zz[u][2], zz[u][3]};
+                    // (nothing is drawn here, but the key stays named: a step closure without it gives the
+                    // two-group V_ZPAIR kernels another register allocation and record addressing)
+                    (void)key;
                 } else if constexpr (kRng) {
                     if constexpr (kStag) {
                         zp[0] = zh[u][0];
@@ -916,8 +795,8 @@ __global__ void __launch_bounds__(NW * 64 * SG, MINW) wc_sde_kernel(const KArgs 
                     f2v e = {E[u][r], E[u][r + 1]}, in = {I[u][r], I[u][r + 1]};
                     f2v ahi = {A[u][r].hi, A[u][r + 1].hi}, alo = {A[u][r].lo, A[u][r + 1].lo};
                     const f2v cpl = kMfma ? f2v{acc[u][r], acc[u][r + 1]} : e * kEinv;
-                    cell_pair_f32<kEs, kLean, kAii0>(pk, e, in, ahi, alo, cpl, f2v{Gc[u][r], Gc[u][r + 1]},
-                                                      f2v{Sl[u][r], Sl[u][r + 1]}, zp[h]);
+                    cell_pair_f32<kAii0>(pk, e, in, ahi, alo, cpl, f2v{Gc[u][r], Gc[u][r + 1]},
+                                         f2v{Sl[u][r], Sl[u][r + 1]}, zp[h]);
                     E[u][r] = e.x;
                     E[u][r + 1] = e.y;
                     I[u][r] = in.x;
@@ -927,99 +806,38 @@ __global__ void __launch_bounds__(NW * 64 * SG, MINW) wc_sde_kernel(const KArgs 
                     A[u][r].lo = alo.x;
                     A[u][r + 1].lo = alo.y;
                 }
-                continue;
-            }
-            if constexpr (kFast && !kHalf) {
-                if constexpr (kZFirst) {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) z[r] = zz[u][r];
-                } else if constexpr (kRng) {
-                    quad_normals_raw(gstep, (uint32_t)(4 * TL(u) + g), key, z);
-                }
+            } else {
+                __builtin_amdgcn_sched_barrier(0);  // fp64: bound live ranges
+                Real z[4] = {0, 0, 0, 0};
+                // the polynomial coefficients as scalar loads from a table, the pointer laundered
+                // here so they are not hoisted out of the step loop into SGPRs (f64m, wc_device.h)
+                const auto cf = [] {
+                    if constexpr (WC_F64_TAB) return f64m::tab_coef();
+                    else return f64m::LitCoef{};
+                }();
+                if constexpr (kRng) quad_normals(gstep, (uint32_t)(4 * TL(u) + g), key, z, cf);
+                // (the divisions by the time constants as a product with the reciprocal plus one
+                // correction step: the quotient to within an ulp, without the IEEE sequence)
+                auto qdiv = [](double x, double y, double iy) {
+                    const double q = x * iy;
+                    return __builtin_fma(__builtin_fma(-y, q, x), iy, q);
+                };
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    // wc:80-83 in fp32 with the constants folded:
-                    //   x' = xE - mu; SE = 1/(1 + 2^(x' * (-sigmaE log2 e)));
-                    //   SI = 1/(1 + 2^(e cIe + in cIi + cI0)); noise = knoise * raw normal
-                    const float e = E[u][r], in = I[u][r];
-                    const float ai = A[u][r].fast();
-                    const float cpl = kMfma ? acc[u][r] : e;
-                    float x = __builtin_fmaf(a_ee, e, Pm);
-                    x = __builtin_fmaf(-ai, in, x);
-                    x = __builtin_fmaf(Gc[u][r], cpl, x);
-                    x = __builtin_fmaf(knoise, z[r], x);
-                    const float SE = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x * Sl[u][r]));
-                    const float SI = __builtin_amdgcn_rcpf(
-                        1.0f + __builtin_amdgcn_exp2f(__builtin_fmaf(e, cIe, __builtin_fmaf(in, cIi, cI0))));
-                    E[u][r] = __builtin_fmaf(dtE, __builtin_fmaf(__builtin_fmaf(-rE, e, 1.0f), SE, -e), e);
-                    I[u][r] = __builtin_fmaf(dtI, __builtin_fmaf(__builtin_fmaf(-rI, in, 1.0f), SI, -in), in);
-#if WC_INC2
-                    A[u][r].add(in * __builtin_fmaf(e, dtA, (float)(-a.rhoE * a.dtSim / a.tau_ip)));
-#else
-                    const float tA = in * dtA;
-                    A[u][r].add(__builtin_fmaf(e, tA, -rhoE * tA));
-#endif
-                }
-                continue;
-            }
-            if constexpr (!kHalf) {
-            // fp64: the polynomial coefficients as scalar loads from a table, the pointer laundered
-            // here so they are not hoisted out of the step loop into SGPRs (f64m, wc_device.h)
-            const auto cf = [] {
-                if constexpr (sizeof(Real) == 8 && WC_F64_TAB) return f64m::tab_coef();
-                else return f64m::LitCoef{};
-            }();
-            if constexpr (kRng) quad_normals(gstep, (uint32_t)(4 * TL(u) + g), key, z, cf);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const Real e = E[u][r], in = I[u][r];
-                const Real ai = A[u][r].template val<Real>();
-                Real gc, sl;
-                if constexpr (kParamRegs) {
-                    gc = Gc[u][r];
-                    sl = Sl[u][r];
-                } else {
-                    const int n = 16 * TL(u) + 4 * g + r;
-                    const size_t o = (size_t)bb * N + (n < N ? n : 0);
-                    gc = n < N ? (Real)a.G[o] : (Real)0;
-                    sl = n < N ? Tr<Real>::slope(a.sigmaE[o]) : (Real)0;
-                }
-                const Real cpl = kMfma ? acc[u][r] : e;
-                const Real xE = a_ee * e - ai * in + gc * cpl + P + sqdtD * z[r];
-                const Real SE = Tr<Real>::sig(xE, mu, sl, cf);
-                const Real xI = a_ei * e - a_ii * in;
-                const Real SI = Tr<Real>::sig(xI, mu, slI, cf);
-                if constexpr (sizeof(Real) == 8) {
-                    // (the divisions by the time constants as a product with the reciprocal plus one
-                    // correction step: the quotient to within an ulp, without the IEEE sequence)
-                    auto qdiv = [](double x, double y, double iy) {
-                        const double q = x * iy;
-                        return __builtin_fma(__builtin_fma(-y, q, x), iy, q);
-                    };
+                    const Real e = E[u][r], in = I[u][r];
+                    const Real ai = A[u][r].template val<Real>();
+                    const Real cpl = kMfma ? acc[u][r] : e;
+                    const Real xE = a_ee * e - ai * in + Gc[u][r] * cpl + P + sqdtD * z[r];
+                    const Real SE = Tr<Real>::sig(xE, mu, Sl[u][r], cf);
+                    const Real xI = a_ei * e - a_ii * in;
+                    const Real SI = Tr<Real>::sig(xI, mu, slI, cf);
                     const Real dE = qdiv(-e + (1 - rE * e) * SE, tauE, itauE);
                     const Real dI = qdiv(-in + (1 - rI * in) * SI, tauI, itauI);
                     const Real dA = qdiv(in * (e - rhoE), tau_ip, itau_ip);
                     E[u][r] = e + dt * dE;
                     I[u][r] = in + dt * dI;
                     A[u][r].add(dt * dA);
-                } else {
-                    E[u][r] = e + dtE * (-e + (1 - rE * e) * SE);
-                    I[u][r] = in + dtI * (-in + (1 - rI * in) * SI);
-                    A[u][r].add(dtA * (in * (e - rhoE)));
                 }
-            }
-            }  // !kHalf
-        }
-        if constexpr (kLean) {
-            if ((s & 15) == 15) {  // fold the running increments into hi (wave-uniform branch)
-#pragma unroll
-                for (int u = 0; u < OT; ++u)
-#pragma unroll
-                    for (int r = 0; r < RW; ++r) {
-                        const float hs = A[u][r].hi + A[u][r].lo;
-                        A[u][r].lo = A[u][r].lo - (hs - A[u][r].hi);
-                        A[u][r].hi = hs;
-                    }
             }
         }
         publish(buf ^ 1);
@@ -1107,14 +925,12 @@ int tiles_for(int N) { return (N + 15) / 16; }
 template <typename Real, int NT, int NW, int VAR, int MINW = 1, int SG = 1>
 int launch_v(const KArgs& ka, const double* sc, void* ws, hipStream_t st, bool prep = true, int extra_blocks = 0,
              size_t lds_floor = 0, int g0 = 0, int ng = -1) {
-    constexpr bool hf = (VAR & (V_F16X3 | V_F16X6)) != 0;
-    constexpr int HP = (VAR & V_F16X6) ? 3 : 2;  // fp16 parts per operand
-    constexpr bool bf = (VAR & (V_BF16X6 | V_BF16X3)) != 0;
     constexpr bool frag_regs = (VAR & V_FRAG_REGS) != 0;
     size_t lds;
-    if constexpr (hf) {
+    if constexpr (sizeof(Real) == 4) {
+        constexpr int HP = 2;  // fp16 parts per operand
         const int total = NT * (NT / 2) * 64;
-        float* scl = static_cast<float*>(ws) + hf_scale_offset(NT, HP);
+        float* scl = static_cast<float*>(ws) + hf_scale_offset(NT);
         if (prep) {  // (prep = false: a later launch of the same call reuses the image)
             hipLaunchKernelGGL(coupling_scale_kernel, dim3(1), dim3(1024), 0, st, sc, ka.N, scl);
             hipLaunchKernelGGL((build_frag_f16<NT, HP>), dim3((total + 255) / 256), dim3(256), 0, st, sc, ka.N,
@@ -1122,12 +938,6 @@ int launch_v(const KArgs& ka, const double* sc, void* ws, hipStream_t st, bool p
         }
         lds = (frag_regs ? 0 : (size_t)NT * (NT / 2) * HP * 64 * 16) +
               (NW > 1 ? (size_t)SG * 2 * (NT / 2) * HP * 64 * 16 : 0);
-    } else if constexpr (bf) {
-        const int total = NT * (NT / 2) * 64;
-        hipLaunchKernelGGL((build_frag_bf16<NT>), dim3((total + 255) / 256), dim3(256), 0, st, sc, ka.N,
-                           static_cast<bf16x8*>(ws));
-        lds = (frag_regs ? 0 : (size_t)NT * (NT / 2) * 3 * 64 * 16) +
-              (NW > 1 ? (size_t)SG * 2 * (NT / 2) * 3 * 64 * 16 : 0);
     } else {
         const int total = NT * NT * 64 * 4;
         if (prep)
@@ -1155,18 +965,19 @@ int launch_v(const KArgs& ka, const double* sc, void* ws, hipStream_t st, bool p
 
 // ---------------- product configurations ----------------
 constexpr int kVarF32 = V_F16X3 | V_FRAG_REGS | V_KAHAN_A;
-#ifndef WC_F64_VAR_EXTRA
-#define WC_F64_VAR_EXTRA 0  // ablation builds only (e.g. V_NO_MFMA, V_NO_RNG)
-#endif
-constexpr int kVarF64 = WC_F64_VAR_EXTRA;
+constexpr int kVarF64 = 0;  // (an fp64 ablation adds V_NO_MFMA or V_NO_RNG here)
 
+// The connectome image's share of the workspace.  fp32: the fp16 image has two parts per chunk and
+// its two scale floats behind it, but this stays the size of a three-part image + 256 bytes, as it
+// was when the image had three bf16 parts: wc_workspace_size() returns it and callers' buffers,
+// and the offset of the normals blocks behind it (zmem_offset), are sized by it.
 size_t frag_bytes(int N, int precision) {
     if (precision == WC_F64) {
         const int nt = tiles_for(N);
         return (size_t)nt * nt * 64 * 4 * 8;
     }
-    const int nt = (tiles_for(N) + 1) & ~1;  // bf16 k-chunks pair tiles
-    return (size_t)nt * (nt / 2) * 3 * 64 * 16 + 256;  // (+ the fp16 scales behind a three-part image)
+    const int nt = (tiles_for(N) + 1) & ~1;  // fp16 k-chunks pair tiles
+    return (size_t)nt * (nt / 2) * 3 * 64 * 16 + 256;
 }
 
 // the two normals blocks of the small-batch path follow the fp32 connectome image (256-B aligned)
@@ -1177,11 +988,9 @@ size_t zmem_offset(int N) { return (frag_bytes(N, WC_F32) + 255) / 256 * 256; }
 // the chip busy, and each busy CU's step is latency-bound; Philox + Box-Muller are about a third
 // of a tile's step.  Each launch covers kZK steps with one workgroup per CU: the integrating
 // workgroups read this block's normals from a buffer, the others draw the next block's
-// (double-buffered, ordered by the launches on one stream; launch_zmem).
-#ifndef WC_ZMEM_HALF
-#define WC_ZMEM_HALF 1  // the normals-block path runs 12 waves per group, half a node tile each (V_HALF2;
-                        // 0: six waves of one tile, 2,500 sims 0.747 vs 0.708 us per step, profiles/r03_half_ab.log)
-#endif
+// (double-buffered, ordered by the launches on one stream; launch_zmem).  The integrating
+// workgroups run 12 waves per group, half a node tile each (V_HALF2; six waves of one tile:
+// 2,500 sims 0.747 vs 0.708 us per step, profiles/r03_half_ab.log).
 constexpr int kZK = 1000;                // steps per launch (a multiple of the drivers' rec_every 20)
 constexpr int kZMinIdle = 32;            // CUs the generator needs at least
 constexpr int kZMaxGroups = 160;         // measured regime: up to 2,560 simulations (the 8-way C3 shard)
@@ -1273,11 +1082,7 @@ int launch_zmem(const KArgs& ka, const double* sc, void* ws, hipStream_t st, int
             rc = rec2 ? launch_v<float, 6, 6, V | V_REC2, 1, 2>(kb, sc, ws, st, k == 0, extra, 96 * 1024)
                       : launch_v<float, 6, 6, V, 1, 2>(kb, sc, ws, st, k == 0, extra, 96 * 1024);
         } else {
-#if WC_ZMEM_HALF
-        rc = launch_v<float, 6, 12, kVarF32 | X | V_ZMEM | V_HALF2>(kb, sc, ws, st, k == 0, cus - groups, 96 * 1024);
-#else
-        rc = launch_v<float, 6, 6, kVarF32 | X | V_ZMEM>(kb, sc, ws, st, k == 0, cus - groups, 96 * 1024);
-#endif
+            rc = launch_v<float, 6, 12, kVarF32 | X | V_ZMEM | V_HALF2>(kb, sc, ws, st, k == 0, cus - groups, 96 * 1024);
         }
         if (rc != WC_OK) return rc;
     }
@@ -1286,9 +1091,6 @@ int launch_zmem(const KArgs& ka, const double* sc, void* ws, hipStream_t st, int
 
 // X: extra variant bits of every product kernel (V_AII0 when a_ii == 0, the reference's value:
 // -2.2% per C3 launch, bit-identical, tools/diag_variants.py 38 vs 41)
-#ifndef WC_SG2
-#define WC_SG2 1  // CUs < groups <= 2 CUs: two six-wave groups per workgroup (0: one group per workgroup)
-#endif
 // V_STAG role mask of the large-batch kernels (four or five groups of three waves per workgroup): bit w
 // = wave slot w draws its normals first.  Waves are placed round-robin on the four SIMDs (masks that
 // give a SIMD one role only, 0x5555 or 0x3333, time like all-A), so SIMD s holds waves s, s + 4,
@@ -1321,24 +1123,18 @@ int launch_f32_nt6(const KArgs& ka, const double* sc, void* ws, hipStream_t st) 
     if (groups <= 2 * cus) {
         if (zpair_shape(groups, cus) && ka.nsteps >= 2 * kZK && ka.zbuf && (ka.rec_every == 0 || kZK % ka.rec_every == 0))
             return launch_zmem<X, true>(ka, sc, ws, st, groups, cus);
-#if WC_SG2
         // CUs < groups <= 2 CUs (the 4-GPU C3 shard: 313 groups): two groups of six one-tile waves per
         // workgroup sharing one LDS image, 12 waves per CU.  One group per workgroup put two
         // six-wave workgroups on groups - CUs of the CUs (1.33 us per step at 5,000 simulations);
         // this runs 1.15 (tools/time_small.py variant 51, profiles/r06/small_sg2.log)
         if (groups > cus)
             return rec2 ? launch_v<float, 6, 6, V2, 1, 2>(ka, sc, ws, st) : launch_v<float, 6, 6, V, 1, 2>(ka, sc, ws, st);
-#endif
         return launch_v<float, 6, 6, kVarF32 | X>(ka, sc, ws, st);
     }
     switch (std::min(5, (groups + cus - 1) / cus)) {
-#ifndef WC_NO_MIX
         // three groups per CU: four waves per group with (2, 2, 1, 1) tiles rotated per group (V_MIX)
         case 3: return rec2 ? launch_v<float, 6, 4, V2 | V_MIX, 1, 3>(ka, sc, ws, st)
                             : launch_v<float, 6, 4, V | V_MIX, 1, 3>(ka, sc, ws, st);
-#else
-        case 3: return rec2 ? launch_v<float, 6, 3, V2, 1, 3>(ka, sc, ws, st) : launch_v<float, 6, 3, V, 1, 3>(ka, sc, ws, st);
-#endif
         case 4: return rec2 ? launch_v<float, 6, 3, VS | V_REC2, 1, 4>(ka, sc, ws, st) : launch_v<float, 6, 3, VS, 1, 4>(ka, sc, ws, st);
         default: return rec2 ? launch_v<float, 6, 3, VS | V_REC2, 1, 5>(ka, sc, ws, st) : launch_v<float, 6, 3, VS, 1, 5>(ka, sc, ws, st);
     }
@@ -1361,23 +1157,17 @@ int launch_f32(const KArgs& ka, const double* sc, void* ws, hipStream_t st) {
 // fp64 parity path: one wave per node tile (NW = NT; E exchanged through LDS), so the
 // latency-bound step of a small batch is spread over NT waves; the per-tile MFMA order is
 // the one-wave kernel's, so the results are the same bits for any NW
-#ifndef WC_F64_SG
-#define WC_F64_SG 2
-#endif
-#ifndef WC_F64_TAIL
-#define WC_F64_TAIL 1
-#endif
-// N 81..96: WC_F64_SG groups of 16 simulations per workgroup share one LDS copy of the fp64
+// N 81..96: kF64SG groups of 16 simulations per workgroup share one LDS copy of the fp64
 // connectome image (73.7 KB), one workgroup per CU.  The groups left over after the full rounds of
-// WC_F64_SG x CUs, when they fit one group per CU, run as a second launch of one-group workgroups
-// (WC_F64_TAIL): a CU's step with six waves takes ~0.7 of the two-group step, so the last round
+// kF64SG x CUs, when they fit one group per CU, run as a second launch of one-group workgroups:
+// a CU's step with six waves takes ~0.7 of the two-group step, so the last round
 // costs that instead of a whole round (1,250 groups on 256 CUs: two full rounds + 226 groups)
+constexpr int kF64SG = 2;
 int launch_f64_nt6(const KArgs& ka, const double* sc, void* ws, hipStream_t st) {
-    constexpr int SG = WC_F64_SG;
+    constexpr int SG = kF64SG;
     const int groups = (ka.B + kSims - 1) / kSims, cus = cu_count();
     const int rem = groups % (SG * cus), full = groups - rem;
-    if (SG == 1 || !WC_F64_TAIL || rem == 0 || rem > cus)
-        return launch_v<double, 6, 6, kVarF64, 1, SG>(ka, sc, ws, st);
+    if (rem == 0 || rem > cus) return launch_v<double, 6, 6, kVarF64, 1, SG>(ka, sc, ws, st);
     if (full > 0) {
         const int rc = launch_v<double, 6, 6, kVarF64, 1, SG>(ka, sc, ws, st, true, 0, 0, 0, full);
         if (rc != WC_OK) return rc;
@@ -1401,61 +1191,23 @@ int launch_f64(const KArgs& ka, const double* sc, void* ws, hipStream_t st) {
 // libwcsde_diag.so (python -m nremmodfc_amd._build --diag), never into the product library
 int launch_diag(int variant, const KArgs& ka, const double* sc, void* ws, hipStream_t st) {
     constexpr int K = V_KAHAN_A;
+    // (the numbers are the tools' interface and are not reused: a gap is a retired variant, which
+    // falls to the default below; docs/CHANGELOG.md records what each one measured)
     switch (variant) {
-        case 0: return launch_v<float, 6, 1, V_FRAG_REGS | K>(ka, sc, ws, st);          // f32 MFMA, 1 wave
-        case 1: return launch_v<float, 6, 3, V_FRAG_REGS | K>(ka, sc, ws, st);          // f32 MFMA, 3 waves
-        case 2: return launch_v<float, 6, 3, K>(ka, sc, ws, st);                        // f32 MFMA, LDS frags
-        case 3: return launch_v<float, 6, 3, V_BF16X6 | V_FRAG_REGS | K>(ka, sc, ws, st);  // product
-        case 4: return launch_v<float, 6, 3, V_BF16X6 | K>(ka, sc, ws, st);
-        case 5: return launch_v<float, 6, 3, V_BF16X6 | V_FRAG_REGS | K, 3>(ka, sc, ws, st);
-        case 6: return launch_v<float, 6, 3, V_BF16X6 | K, 4>(ka, sc, ws, st);
-        case 7: return launch_v<float, 6, 2, V_BF16X6 | V_FRAG_REGS | K>(ka, sc, ws, st);
-        case 8: return launch_v<float, 6, 2, V_BF16X6 | K, 3>(ka, sc, ws, st);
-        case 9: return launch_v<float, 6, 6, V_BF16X6 | K>(ka, sc, ws, st);
-        case 10: return launch_v<float, 6, 1, V_BF16X6 | V_FRAG_REGS | K>(ka, sc, ws, st);
-        case 11: return launch_v<float, 6, 3, V_BF16X6 | V_FRAG_REGS | K | V_NO_RNG>(ka, sc, ws, st);
-        case 12: return launch_v<float, 6, 3, V_BF16X6 | V_FRAG_REGS | K | V_NO_MFMA>(ka, sc, ws, st);
-        case 13: return launch_v<float, 6, 3, V_BF16X3 | V_FRAG_REGS | K>(ka, sc, ws, st);
-        case 14: return launch_v<float, 6, 3, V_BF16X6 | V_FRAG_REGS>(ka, sc, ws, st);  // fp64 a_ie
-        // one workgroup per CU: SG groups of 16 sims share the LDS connectome image
-        case 15: return launch_v<float, 6, 3, V_BF16X6 | K, 1, 5>(ka, sc, ws, st);
-        case 16: return launch_v<float, 6, 3, V_BF16X6 | K, 1, 4>(ka, sc, ws, st);
-        case 17: return launch_v<float, 6, 3, V_BF16X6 | K, 1, 3>(ka, sc, ws, st);
-        case 18: return launch_v<float, 6, 2, V_BF16X6 | K, 1, 5>(ka, sc, ws, st);
-        case 19: return launch_v<float, 6, 6, V_BF16X6 | K, 1, 2>(ka, sc, ws, st);
-        // node-major record buffering (needs rec_ld % 4 == 0, E records only)
-        case 20: return launch_v<float, 6, 3, V_BF16X6 | K | V_REC4, 1, 5>(ka, sc, ws, st);
-        case 21: return launch_v<float, 6, 3, V_BF16X6 | K | V_REC2, 1, 5>(ka, sc, ws, st);
-        case 22: return launch_v<float, 6, 3, V_BF16X6 | V_FRAG_REGS | K | V_REC4>(ka, sc, ws, st);
-        case 23: return launch_v<float, 6, 3, V_BF16X6 | K, 1, 5>(ka, sc, ws, st);  // = 15, node-major records
-        // ablations of the grouped product kernel (15): noise off, coupling off
-        case 24: return launch_v<float, 6, 3, V_BF16X6 | K | V_NO_RNG, 1, 5>(ka, sc, ws, st);
-        case 25: return launch_v<float, 6, 3, V_BF16X6 | K | V_NO_MFMA, 1, 5>(ka, sc, ws, st);
-        // fp16 x3 coupling: grouped (as 15), register-resident (as 3)
+        // (26..34 record node-major, see wc_diag_integrate)
+        // five groups per workgroup sharing the LDS image; one group with its fragments in registers
         case 26: return launch_v<float, 6, 3, V_F16X3 | K, 1, 5>(ka, sc, ws, st);
         case 27: return launch_v<float, 6, 3, V_F16X3 | V_FRAG_REGS | K>(ka, sc, ws, st);
-        // the grouped fp16 product (26) with the normals drawn before / interleaved with the MFMAs
-        case 28: return launch_v<float, 6, 3, V_F16X3 | K | V_ZFIRST, 1, 5>(ka, sc, ws, st);
-        case 29: return launch_v<float, 6, 3, V_F16X3 | K | V_ZFIRST | V_ILV, 1, 5>(ka, sc, ws, st);
-        case 30: return launch_v<float, 6, 3, V_F16X3 | K | V_ZFIRST | V_ILV2, 1, 5>(ka, sc, ws, st);
-        // small batches (strong-scaling shards): more waves per group of 16 simulations
+        // small batches (strong-scaling shards): six waves per group of 16 simulations
         case 31: return launch_v<float, 6, 6, V_F16X3 | V_FRAG_REGS | K>(ka, sc, ws, st);
-        case 32: return launch_v<float, 6, 6, V_F16X3 | V_FRAG_REGS | K | V_ZFIRST>(ka, sc, ws, st);
-        case 33: return launch_v<float, 6, 3, V_F16X3 | V_FRAG_REGS | K | V_ZFIRST>(ka, sc, ws, st);
         case 34: return launch_v<float, 6, 6, V_F16X3 | K>(ka, sc, ws, st);
-        case 35: return launch_v<float, 6, 6, V_F16X3 | V_FRAG_REGS | K | V_ZFIRST | V_ILV2>(ka, sc, ws, st);
-        case 36: return launch_v<float, 6, 2, V_F16X3 | V_FRAG_REGS | K | V_ZFIRST>(ka, sc, ws, st);
-        // 37: the C3 product configuration (SG = 5, paired records) with the round-2 one-cell-per-instruction update
-        case 37: return launch_v<float, 6, 3, V_F16X3 | K | V_REC2 | V_SCALAR, 1, 5>(ka, sc, ws, st);
         // the C3 product kernel (launch_f32_nt6's SG = 5 case, time-major records) and its ablations:
         // noise off, coupling MFMAs off
         case 38: return launch_v<float, 6, 3, V_F16X3 | V_KAHAN_A, 1, 5>(ka, sc, ws, st);
         case 39: return launch_v<float, 6, 3, V_F16X3 | V_KAHAN_A | V_NO_RNG, 1, 5>(ka, sc, ws, st);
         case 40: return launch_v<float, 6, 3, V_F16X3 | V_KAHAN_A | V_NO_MFMA, 1, 5>(ka, sc, ws, st);
-        // round 3: the C3 product kernel (38) with the a_ii = 0 sigmoid (bit-identical), the lean a_ie sum, both
+        // the C3 product kernel (38) with the a_ii = 0 sigmoid (bit-identical)
         case 41: return launch_v<float, 6, 3, V_F16X3 | V_KAHAN_A | V_AII0, 1, 5>(ka, sc, ws, st);
-        case 42: return launch_v<float, 6, 3, V_F16X3 | V_KAHAN_A | V_LEAN, 1, 5>(ka, sc, ws, st);
-        case 43: return launch_v<float, 6, 3, V_F16X3 | V_KAHAN_A | V_LEAN | V_AII0, 1, 5>(ka, sc, ws, st);
         // the small-batch product kernel (6 waves, one tile each) and its ablations: coupling MFMAs off,
         // noise off, both off (where the latency-bound step of a strong-scaling shard goes)
         case 44: return launch_v<float, 6, 6, kVarF32 | V_AII0>(ka, sc, ws, st);
@@ -1471,8 +1223,6 @@ int launch_diag(int variant, const KArgs& ka, const double* sc, void* ws, hipStr
         case 54: return launch_v<float, 6, 6, V_F16X3 | V_KAHAN_A | V_AII0, 1, 3>(ka, sc, ws, st);
         case 55: return launch_v<float, 6, 3, V_F16X3 | V_KAHAN_A | V_AII0, 1, 3>(ka, sc, ws, st);
         case 56: return launch_v<float, 6, 4, V_F16X3 | V_KAHAN_A | V_AII0 | V_MIX, 1, 3>(ka, sc, ws, st);
-        // the C3 product configuration (= 41, time-major records as the bench) with the >= 24-bit coupling
-        case 58: return launch_v<float, 6, 3, V_F16X6 | V_KAHAN_A | V_AII0, 1, 5>(ka, sc, ws, st);
         // 41 with its constants two per VGPR pair; the same with wave roles (the product: WCSDE_STAGGER picks the mask)
         case 60: return launch_v<float, 6, 3, V_F16X3 | V_KAHAN_A | V_AII0 | V_PKC, 1, 5>(ka, sc, ws, st);
         case 61: return launch_v<float, 6, 3, V_F16X3 | V_KAHAN_A | V_AII0 | V_PKC | V_STAG, 1, 5>(ka, sc, ws, st);
@@ -1548,12 +1298,8 @@ const char* wc_last_error(void) { return wc_errbuf(); }
 size_t wc_workspace_size(int B, int N, int precision) {
     if (N <= 0 || B <= 0) return 0;
     if (tiles_for(N) > kMaxTiles) return wc_large_workspace_size(B, N, precision);
-    // the diagnostic f32-MFMA variants need the native image; size for the larger
-    const int nt = tiles_for(N);
-    const size_t native = (size_t)nt * nt * 64 * 4 * (precision == WC_F64 ? 8 : 4);
-    size_t need = frag_bytes(N, precision);
-    if (precision == WC_F32 && zmem_eligible_shape(B, N)) need = zmem_offset(N) + 2 * zmem_block_bytes(B);
-    return need > native ? need : native;
+    if (precision == WC_F32 && zmem_eligible_shape(B, N)) return zmem_offset(N) + 2 * zmem_block_bytes(B);
+    return frag_bytes(N, precision);
 }
 
 int wc_integrate(const wc_params* p, int precision, int B, int N, const double* sc, const double* G,
@@ -1591,10 +1337,11 @@ int wc_diag_integrate(int variant, const wc_params* p, int B, int N, const doubl
                       int64_t nsteps, double tau_ip, int64_t rec_every, void* recE, void* workspace,
                       size_t ws_bytes, void* stream) {
     KArgs ka;
-    // variants 20..37 record node-major into a dense [B*N][ld] buffer, ld = n_rec rounded up to 4
-    // (38..40, the product's ablations, record time-major as the C3 pipeline does)
+    // variants below 38 (26, 27, 31, 34) record node-major into a dense [B*N][ld] buffer, ld = n_rec
+    // rounded up to 4 (38 and up, the product's kernels and ablations, record time-major as the C3
+    // pipeline does)
     const int64_t n_rec = rec_every > 0 ? (nsteps + rec_every - 1) / rec_every : 0;
-    const bool nm = variant >= 20 && variant < 38;
+    const bool nm = variant < 38;
     const int64_t ld = (nm && rec_every > 0) ? (n_rec + 3) & ~int64_t(3) : 0;
     int rc = make_args(ka, p, WC_F32, B, N, sc, G, sigmaE, keys, E, I, A, step0, nsteps, tau_ip, rec_every, ld,
                        recE, nullptr, nullptr, workspace, ws_bytes);

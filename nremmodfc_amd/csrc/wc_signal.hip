@@ -182,20 +182,11 @@ __device__ __forceinline__ void emit(const BoldArgs& a, const BoldLayout& L, dou
 // COPY: time-major fp32 input, also written out node-major (copy[c*copy_ld + tt])
 // through a 256-column x 32-sample LDS tile flushed as 128-B rows.
 constexpr int kCopyT = 32;
-#ifndef WC_BOLD_PINGPONG
-#define WC_BOLD_PINGPONG 1  // the steady loop's two sample batches in static ping-pong buffers (0: one
-                            // buffer copied per batch; 1.3% slower, profiles/r03_ab_bold_pp.log)
-#endif
-#ifndef WC_BOLD_BATCH
-#define WC_BOLD_BATCH 16    // samples per load batch (divides kCopyT)
-#endif
-constexpr int kBat = WC_BOLD_BATCH;
-#ifndef WC_BOLD_COPY_WPS
-#define WC_BOLD_COPY_WPS 4  // workgroups (of 4 waves) per CU for the steady copy instantiation: 128 VGPRs,
-                            // 8 spilled, 6% faster than 3 (tools/ab_multi.sh, profiles/r03_ab_bold.log)
-#endif
+constexpr int kBat = 16;     // samples per load batch (divides kCopyT)
+constexpr int kCopyWps = 4;  // workgroups (of 4 waves) per CU for the steady copy instantiation: 128 VGPRs,
+                             // 8 spilled, 6% faster than 3 (tools/ab_multi.sh, profiles/r03_ab_bold.log)
 template <typename ET, bool COPY, bool STEADY, bool BP = false>
-__global__ void __launch_bounds__(256, (STEADY && sizeof(ET) == 4) ? (COPY ? WC_BOLD_COPY_WPS : 4) : 1) bold_chunk_kernel(const BoldArgs a, const ET* __restrict__ E, int64_t e_ld,
+__global__ void __launch_bounds__(256, (STEADY && sizeof(ET) == 4) ? (COPY ? kCopyWps : 4) : 1) bold_chunk_kernel(const BoldArgs a, const ET* __restrict__ E, int64_t e_ld,
                                                          int64_t t0, int64_t Tc, double* __restrict__ st,
                                                          float* __restrict__ copy, int64_t copy_ld) {
     const int64_t c0 = (int64_t)blockIdx.x * blockDim.x;
@@ -421,10 +412,10 @@ __global__ void __launch_bounds__(256, (STEADY && sizeof(ET) == 4) ? (COPY ? WC_
     };
     ET xa[kBat];
     load(xa, 0);
-#if WC_BOLD_PINGPONG
     if constexpr (STEADY) {
-        // two batches per iteration with static buffers: no register copy of in-flight loads (a copy
-        // would wait for them, vmcnt retiring in order)
+        // two batches per iteration in static ping-pong buffers: no register copy of in-flight loads (a
+        // copy would wait for them, vmcnt retiring in order; one buffer copied per batch measured
+        // 1.3% slower, profiles/r03_ab_bold_pp.log)
         ET xb[kBat];
         int64_t tb = 0;
         for (; tb + kBat < Tc; tb += 2 * kBat) {
@@ -434,16 +425,8 @@ __global__ void __launch_bounds__(256, (STEADY && sizeof(ET) == 4) ? (COPY ? WC_
             process(xb, tb + kBat);
         }
         if (tb < Tc) process(xa, tb);
-    } else
-#endif
-    for (int64_t tb = 0; tb < Tc; tb += kBat) {
-        if (STEADY) {
-            ET xb[kBat];
-            if (tb + kBat < Tc) load(xb, tb + kBat);
-            process(xa, tb);
-#pragma unroll
-            for (int j = 0; j < kBat; ++j) xa[j] = xb[j];
-        } else {
+    } else {
+        for (int64_t tb = 0; tb < Tc; tb += kBat) {
             if (tb > 0) load(xa, tb);
             process(xa, tb);
         }

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Ablation builds of one source (CPU side): csrc/<SRC>.hip with extra -D flags, linked with the
 # product objects of every other source into tools/dbg/lib<SRC>_<name>.so.
-#   bash tools/dbg/variants.sh SRC NAME=-DFLAG ...      (e.g. wc_sde half=-DWC_ZMEM_HALF=1)
+#   bash tools/dbg/variants.sh SRC NAME=-DFLAG ...      (e.g. wc_sde tab=-DWC_F64_TAB=1)
 set -eu
 cd "$(dirname "$0")/../.."
 SRC=$1; shift

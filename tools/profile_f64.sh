@@ -17,7 +17,7 @@ import collections, json, sys
 sys.path.insert(0, "tools")
 from pmc_summary import lib_stamp, summary
 stamp = lib_stamp("gpurun_out/prof64/sqa", "gpurun_out/prof64/sqb")
-# a launch may be two dispatches (the full two-group rounds + the one-group tail, WC_F64_TAIL):
+# a launch may be two dispatches (the full two-group rounds + the one-group tail launch of launch_f64_nt6):
 # per-launch totals are the sums of the per-dispatch averages of every wc_sde_kernel<double> form
 def total(s):
     out = collections.Counter()

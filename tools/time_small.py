@@ -22,7 +22,7 @@ from nremmodfc_amd.model import Batch, driver_params  # noqa: E402
 
 
 def main():
-    variants = [int(v) for v in (sys.argv[1] if len(sys.argv) > 1 else "27,31,32,33,34,35,36").split(",")]
+    variants = [int(v) for v in (sys.argv[1] if len(sys.argv) > 1 else "27,31,34").split(",")]
     batches = [int(b) for b in (sys.argv[2] if len(sys.argv) > 2 else "1250,2500,5000,10000").split(",")]
     steps = int(os.environ.get("DIAG_STEPS", "4000"))
     sc = datasets.load_sc()
