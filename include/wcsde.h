@@ -591,6 +591,45 @@ int wc_graph_louvain(int B, int R, int N, const double* obj, const double* norm,
                      const uint64_t* seeds, int32_t* ci, double* q, int32_t* info, void* stream);
 int wc_graph_agreement(int B, int R, int N, const int32_t* ci, double* D, void* stream);
 
+/* Partition search on matrices with weights of both signs (wc_louvain_sign.hip).
+ *
+ * wc_graph_louvain_sign: modularity_louvain_und_sign (graph_utils.py:697-855; Rubinov & Sporns 2011)
+ *   for every pair of a matrix and a seed.  w [B][N][N] fp64, any signs; seeds [R] uint64; gamma
+ *   finite; qtype 0 "sta", 1 "pos", 2 "smp", 3 "gja", 4 "neg".
+ *     ci   [B][R][N]  int32, labels 0 .. K-1: the reference's final labelling minus 1
+ *     q    [B][R]     the modularity of the last level
+ *     info [B][R][2]  int32, levels (passes of the outer loop) and node sweeps in all; may be NULL
+ *   W0 = W (W > 0), W1 = -W (W < 0); kn0, kn1 their column sums and s0, s1 the sums of those, all
+ *   taken in ascending index order; (d0, d1) = (1/s0, 1/(s0+s1)) sta, (1/s0, 0) pos, (1/s0, 1/s1)
+ *   smp, (1/(s0+s1), 1/(s0+s1)) gja, (0, 1/s1) neg; then s0 == 0 gives s0 = 1, d0 = 0 and s1 == 0
+ *   gives s1 = 1, d1 = 0.  Per level, sweeps over the current nodes until none moves; node u of module
+ *   ma has, one rounding per operation and no fma, as numpy evaluates the reference's line,
+ *     dQ0 = ((knm0[u,m] + W0[u,u]) - knm0[u,ma]) - ((gamma kn0[u]) ((km0[m] + kn0[u]) - km0[ma])) / s0,
+ *     dQ1 the same on W1, dQ = d0 dQ0 - d1 dQ1 (both products rounded), dQ[ma] = 0,
+ *   and moves where max dQ > 1e-10 to the lowest index that attains the maximum, an empty module
+ *   included.  Between levels the modules are relabelled as np.unique does and W0, W1 are pooled
+ *   over module pairs, the upper triangle computed and mirrored; the level's modularity is
+ *   q = d0 (tr W0 - sum(W0 W0) / s0) - d1 (tr W1 - sum(W1 W1) / s1), the sum over all entries of the
+ *   matrix product taken as the sum of the squared column sums (the pooled matrix is symmetric);
+ *   levels go on while q - q before > 1e-10, from q = -1, 0, and the last level's ci and q are
+ *   returned whether it improved or not.  An all-zero matrix gives N singletons and q = 0.
+ *   The visiting order is wc_graph_louvain's: sweeps numbered t = 0, 1, 2, ... over all levels of a
+ *   run, the same Philox keys.
+ *   A matrix with a NaN or inf gets ci = -1, q = NaN and info = 0 in all its runs; a run whose level
+ *   has not settled after 1000 sweeps, or that would start a 301st level (the reference raises in
+ *   both cases) gets ci = -1 and q = NaN; nothing else is affected.
+ *   Workspace: W0 and W1 of the pooled levels lie in global memory, one slot of 16 N^2 bytes per
+ *   workgroup; the grid is min(B R, ws_bytes / slot) workgroups, which stride over the problems.
+ *   ws_bytes below one slot: WC_EINVAL.  Fixed summation order, no atomics: a (matrix, seed) pair gives
+ *   the same bits alone, in any batch and with any ws_bytes.
+ *   Checked before any device work: B, R >= 1, 2 <= N <= 96 (more: WC_EUNSUPPORTED), B R < 2^31, qtype
+ *   in 0 .. 4, gamma finite; w, seeds, ci, q, workspace not NULL; fp64 and uint64 arrays and the
+ *   workspace 8-byte, int32 arrays 4-byte aligned; no output, the used part of the workspace
+ *   included, overlapping an input or another output. */
+int wc_graph_louvain_sign(int B, int R, int N, const double* w, double gamma, int qtype,
+                          const uint64_t* seeds, int32_t* ci, double* q, int32_t* info,
+                          void* workspace, size_t ws_bytes, void* stream);
+
 /* Dynamic functional connectivity (wc_fcd.hip): sliding-window FC with its FCD matrix (Hansen et al.
  * 2015) and the phase-coherence FCD (Deco & Kringelbach 2016).  The reference computes neither; these
  * definitions are the contract (tests/fcd_reference.py restates them in numpy).

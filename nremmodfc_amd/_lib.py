@@ -98,6 +98,8 @@ _SIGNATURES = {
     "wc_graph_modules": (c_int, [c_int, c_int, c_int, c_vp, c_vp, c_int, c_int, c_dbl, c_vp, c_vp, c_vp, c_vp]),
     "wc_graph_louvain": (c_int, [c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "wc_graph_agreement": (c_int, [c_int, c_int, c_int, c_vp, c_vp, c_vp]),
+    "wc_graph_louvain_sign": (c_int, [c_int, c_int, c_int, c_vp, c_dbl, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz,
+                                      c_vp]),
     "wc_fcd_workspace_size": (c_sz, [c_int, c_int, c_int, c_int, c_int]),
     "wc_fcd": (c_int, [c_int, c_int, c_int, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "wc_fcd_phase": (c_int, [c_int, c_int, c_int, c_vp, c_vp, c_vp]),

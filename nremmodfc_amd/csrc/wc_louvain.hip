@@ -24,51 +24,19 @@
 #include <stdint.h>
 #include "wc_common.h"
 #include "wc_device.h"
+#include "wc_louvain_dev.h"
 
 namespace {
 
-constexpr int kMaxN = 96;
-constexpr int kWave = 64;           // threads of a Louvain workgroup: one wave
-constexpr int kSweepGuard = 1000;   // graph_utils.py:1071
-constexpr double kTol = 1e-10;      // :1066, :1081
+using wclv::kMaxN;
+using wclv::kWave;
+using wclv::kSweepGuard;
+using wclv::kTol;
+using wclv::wave_argmax;
+using wclv::relabel;
 constexpr int kAgThreads = 256;
 constexpr int kAgChunk = 32;        // partitions staged in LDS at a time
 constexpr int kAgPairs = kMaxN * kMaxN / kAgThreads;  // pairs (i, j) per thread: 36
-
-// np.max and np.argmax of one value per lane: the largest, at the lowest index that attains it.
-// Every lane returns the same pair.  All 64 lanes must be active.
-__device__ __forceinline__ void wave_argmax(double& v, int& idx) {
-#pragma unroll
-    for (int off = kWave / 2; off; off >>= 1) {
-        const double ov = __shfl_xor(v, off);
-        const int oi = __shfl_xor(idx, off);
-        if (ov > v || (ov == v && oi < idx)) {
-            v = ov;
-            idx = oi;
-        }
-    }
-}
-
-// np.unique(lab, return_inverse=True): lab[i] <- the number of distinct values below lab[i], values
-// in [0, n).  Returns the number of distinct values.  The wave is synchronised on entry and on return.
-__device__ int relabel(int n, int* lab, int* used, int* newlab) {
-    const int lane = threadIdx.x;
-    for (int v = lane; v < n; v += kWave) used[v] = 0;
-    __syncthreads();
-    for (int i = lane; i < n; i += kWave) used[lab[i]] = 1;  // equal values from several lanes
-    __syncthreads();
-    for (int v = lane; v < n; v += kWave) {
-        int c = 0;
-        for (int x = 0; x < v; ++x) c += used[x];
-        newlab[v] = c;
-    }
-    int K = 0;
-    for (int x = 0; x < n; ++x) K += used[x];
-    __syncthreads();
-    for (int i = lane; i < n; i += kWave) lab[i] = newlab[lab[i]];
-    __syncthreads();
-    return K;
-}
 
 // ---- wc_graph_louvain: one wave per (matrix, seed) ----
 __global__ void __launch_bounds__(kWave) louvain_kernel(int R, int N, const double* __restrict__ obj_all,
@@ -140,24 +108,7 @@ __global__ void __launch_bounds__(kWave) louvain_kernel(int R, int N, const doub
                 break;
             }
             moved = false;
-            // the order of sweep t: the stable argsort of n Philox words
-            for (int i = lane; i < n; i += kWave) {
-                uint32_t x[4];
-                wcdev::philox_ctr(t, (uint32_t)i >> 2, seed, x);
-                const int k = i & 3;
-                keys[i] = k == 0 ? x[0] : (k == 1 ? x[1] : (k == 2 ? x[2] : x[3]));
-            }
-            __syncthreads();
-            for (int i = lane; i < n; i += kWave) {
-                const uint32_t k = keys[i];
-                int rank = 0;
-                for (int j = 0; j < n; ++j) {
-                    const uint32_t kj = keys[j];
-                    rank += kj < k || (kj == k && j < i);
-                }
-                order[rank] = i;
-            }
-            __syncthreads();
+            wclv::sweep_order(t, seed, n, keys, order);
             ++t;
             for (int p = 0; p < n; ++p) {
                 const int u = order[p], ma = Mb[u];

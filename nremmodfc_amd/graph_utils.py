@@ -23,6 +23,8 @@ the sweep path.
 """
 import numpy as np
 
+from .partition_np import consensus_und, modularity_louvain_und_sign  # noqa: F401  (wc_louvain_sign.hip)
+
 
 def get_uptri(x):
     """Strict upper triangle, row-major (graph_utils.py:92-105)."""
@@ -270,8 +272,8 @@ def community_louvain(W, gamma=1, ci=None, B="modularity", seed=None):
     does NOT reproduce the partition numpy's generator gives for that seed, only the reference's
     algorithm under the engine's order.  The same seed always gives the same result.
     Not built: B 'negative_sym' and 'negative_asym' (unreachable in the reference, which raises on
-    negative weights first), modularity_louvain_und_sign, consensus_und, modularity_und's spectral
-    search, N > 96."""
+    negative weights first), modularity_und's spectral search, N > 96.  Matrices with weights of both
+    signs go to modularity_louvain_und_sign."""
     import os
     a, lab, obj = _louvain_args("community_louvain", W, ci, B)
     if seed is None:
