@@ -729,6 +729,65 @@ int wc_kmeans_update(int64_t R, int N, int K, const double* x, const int32_t* la
 int wc_state_stats(int B, int M, int K, const int32_t* labels, double* occupancy, double* dwell,
                    double* trans, void* stream);
 
+/* Surrogate-tested functional connectivity (wc_surrogate.hip): the reference's
+ * probabilistic_thresholding (graph_utils.py:220-265) for a batch.  It multiplies the FFT of the
+ * mean-free series y [L][N] by exp(i r), r [L] the random phases rv [L/2][N] stacked over their own
+ * reverse, and correlates the real part of the inverse FFT.  That real part is the inverse FFT of
+ * the Hermitian part of the product, so with h = L/2 the spectrum of surrogate column n is
+ *     X_n(k) = Y_n(k) (exp(i rv[k][n]) + exp(-i rv[k-1][n])) / 2    for 1 <= k <= h - 1,
+ *     X_n(h) = Y_n(h) cos(rv[h-1][n]),
+ * bin 0 being removed by the correlation's own centring, and by Parseval the surrogate's correlation
+ * matrix is the Gram matrix, normalised by its diagonal, of the real rows
+ *     sqrt(2) Re X(k), sqrt(2) Im X(k) (k = 1 .. h - 1), X(h):    L - 1 rows, no inverse transform.
+ * The amplitude spectrum is not preserved: that is the reference's surrogate and is reproduced.
+ *
+ * Phases.  The phases are the engine's: rv[k][n] of a surrogate with seed s is 2 pi w 2^-32, w the
+ * word n & 3 of the Philox4x32-10 block with counter (k lo32, (k hi16 << 16) | n >> 2, s lo32,
+ * s hi32) and key (WC_PHILOX_KEY0, WC_PHILOX_KEY1): the block wc_graph_louvain's visiting order
+ * draws with (t, i >> 2, seed).  They depend on the seed, k and n only, not on the simulation, as
+ * the reference's np.random.seed(i + 1) gives every series the same random_vector.  The kernel
+ * takes cos and sin of 2 pi w 2^-32 as cospi and sinpi of w 2^-31, which is exact in its argument.
+ *
+ * wc_surrogate_fc: spec [L/2 + 1][B N] complex, interleaved (re, im): the DFT at bins 0 .. L/2 of
+ *   the mean-free columns of x [L][B][N], which wc_spectrogram gives with nperseg = L, noverlap = 0,
+ *   a window of ones, detrend 1, scale 1 and WC_SPEC_COMPLEX; seeds [S] uint64.
+ *     sfc [B][S][P]  the strict upper triangle, row-major, P = N (N - 1) / 2, of the correlation
+ *                    matrix of surrogate s of simulation b: the Gram product in fp64, the rows taken
+ *                    four at a time in the order k = 1 .. h, real before imaginary (one
+ *                    v_mfma_f64_16x16x4_f64 per 16 x 16 tile), g_ij (1 / sqrt g_ii) (1 / sqrt g_jj)
+ *                    clipped to [-1, 1] as wc_corrcoef; a column without power (a constant series)
+ *                    or with a NaN or an infinity gives NaN in its pairs (0 inf, as numpy's 0 / 0).
+ *   No atomics, one fixed order: a (simulation, surrogate) pair gives the same bits alone and at any
+ *   position of any batch.
+ *
+ * wc_surrogate_test: fc [B][N][N] the FC of the series themselves (wc_corrcoef), of which the
+ *   strict upper triangle is read; sfc as above; 0 < alpha < 1.  Per pair q = (i, j), i < j:
+ *     mu = (sum_s sfc[b][s][q]) / S, sd = sqrt((sum_s (sfc[b][s][q] - mu)^2) / S), both sums in the
+ *     order of s (two passes; the population deviation, as stats.norm.fit), z = (fc[b][i][j] - mu) / sd,
+ *     p = 1 - Phi(z), evaluated as the reference's 1 - stats.norm.cdf: with t = z / sqrt 2,
+ *     Phi = 1/2 + erf(t) / 2 where |t| < 1, else erfc(|t|) / 2 or, for t > 0, 1 minus that; so p
+ *     saturates to exactly 0 from z of about 8.3 on, as the reference's.  sd > 0 false: p = NaN (SciPy
+ *     refuses a scale of 0).
+ *   Per matrix the Benjamini-Hochberg adjustment over its P values, as
+ *   scipy.stats.false_discovery_control(p, method='bh'): sorted ascending, p_(r) (P / r) for rank r =
+ *   1 .. P (the quotient first), the running minimum from the top, at most 1, back in place.  Equal
+ *   p-values get equal results in any order.
+ *     p_adj  [B][N][N]  the adjusted p-values, symmetric, diagonal 0 (the reference's matrix_recon)
+ *     fc_adj [B][N][N]  fc[b][i][j] (p_adj < alpha ? 1 : 0) at (i, j) and (j, i), diagonal 0
+ *     mu, sd, p [B][P]  the pairs' statistics and unadjusted p-values; each may be NULL
+ *   A matrix with a p that is not finite (a constant or non-finite column, a pair whose surrogate
+ *   values all coincide, a NaN in fc) has p_adj and fc_adj NaN throughout, the diagonal included;
+ *   mu, sd and p are written as computed; no other matrix is touched.
+ *
+ * Both: B >= 1, 2 <= N <= 96 (more: WC_EUNSUPPORTED), S >= 2, B S < 2^31; wc_surrogate_fc: L even
+ * (odd: WC_EINVAL, the reference raises there), 4 <= L <= 4096 (more: WC_EUNSUPPORTED); pointers
+ * not NULL (mu, sd, p apart), spec 16-byte and every other array 8-byte aligned, no output
+ * overlapping an input or another output; all of it checked before any device work. */
+int wc_surrogate_fc(int B, int N, int L, int S, const double* spec, const uint64_t* seeds,
+                    double* sfc, void* stream);
+int wc_surrogate_test(int B, int N, int S, const double* fc, const double* sfc, double alpha,
+                      double* p_adj, double* fc_adj, double* mu, double* sd, double* p, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

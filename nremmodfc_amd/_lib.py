@@ -108,6 +108,8 @@ _SIGNATURES = {
     "wc_kmeans_workspace_size": (c_sz, [c_i64, c_int, c_int, c_int]),
     "wc_kmeans_update": (c_int, [c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "wc_state_stats": (c_int, [c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "wc_surrogate_fc": (c_int, [c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp]),
+    "wc_surrogate_test": (c_int, [c_int, c_int, c_int, c_vp, c_vp, c_dbl, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
 }
 
 

@@ -10,20 +10,24 @@ stack; betweenness_wei and betweenness_bin through sigchain.graph_betweenness,
 participation_coef and module_degree_zscore through
 sigchain.graph_module_measures (which also gives the modularity Q of a given
 partition); community_louvain, agreement and get_agreement_matrix through
-sigchain.graph_louvain, graph_agreement and graph_consensus_matrix.  torch and
+sigchain.graph_louvain, graph_agreement and graph_consensus_matrix;
+modularity_louvain_und_sign and consensus_und through partition (partition_np);
+probabilistic_thresholding, the surrogate test that decides which FC entries are
+links at all, through surrogate.fc_surrogate_test (surrogate_np).  torch and
 the library are imported on first use, so importing this module stays light.
 
-Of the partition search, outside: the 'negative_sym' and 'negative_asym'
+Outside: of the partition search the 'negative_sym' and 'negative_asym'
 objectives (unreachable in the reference, which refuses negative weights
-first), modularity_louvain_und_sign, consensus_und (it calls that unseeded
-signed variant), the spectral search of modularity_und (its kci form is
-graph_module_measures' Q), and N > 96.  The rest of the 2,600-line toolbox
-(rich club, assortativity, signed and null-model variants) is analysis outside
-the sweep path.
+first), the spectral search of modularity_und (its kci form is
+graph_module_measures' Q), and N > 96; probabilistic_thresholding2, the
+rank-remapped variant of the surrogate test.  The rest of the 2,600-line
+toolbox (rich club, assortativity, null-model variants) is analysis outside the
+sweep path.
 """
 import numpy as np
 
 from .partition_np import consensus_und, modularity_louvain_und_sign  # noqa: F401  (wc_louvain_sign.hip)
+from .surrogate_np import probabilistic_thresholding  # noqa: F401  (wc_surrogate.hip)
 
 
 def get_uptri(x):
