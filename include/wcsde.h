@@ -788,6 +788,84 @@ int wc_surrogate_fc(int B, int N, int L, int S, const double* spec, const uint64
 int wc_surrogate_test(int B, int N, int S, const double* fc, const double* sfc, double alpha,
                       double* p_adj, double* fc_adj, double* mu, double* sd, double* p, void* stream);
 
+/* Degree- and strength-preserving null models of signed undirected matrices (wc_nullmodel.hip): the
+ * reference's randmio_und_signed (graph_utils.py:2165-2217) and null_model_und_sign (:2219-2338;
+ * Rubinov & Sporns 2011), for every pair of a matrix and a seed.  tests/nullmodel_reference.py
+ * restates this text in numpy.
+ *
+ * Both: w [B][N][N] fp64, any signs, exactly symmetric; the diagonal is not used: it is cleared
+ * (:2264).  seeds [R] uint64.  info [B][R][3] int32: the effective rewirings eff, the draws consumed
+ * (modulo 2^32), and a status: 0, or 1 to 3 as below; may be NULL.
+ *
+ * Rewiring.  itr = bin_swaps (N (N - 1) / 2) iterations; bin_swaps = 0 rewires nothing.  An iteration
+ *   makes at most A = round(N / 2) + 1 attempts, the rounding half to even as np.round (N = 5: 2,
+ *   N = 7: 4).  An attempt takes four distinct nodes (a, b, c, d) and, with signs in {-, 0, +}, swaps
+ *   where sign(ab) == sign(cd), sign(ad) == sign(cb) and sign(ab) != sign(ad): (ad, da) <- ab,
+ *   (ab, ba) <- ad, (cb, bc) <- cd, (cd, dc) <- cb, the old values; that ends the iteration and counts
+ *   in eff.  The nodes are the engine's: the draws of a run are numbered d = 0, 1, 2, ... over all its
+ *   iterations, draw d is the Philox block above with step = d, quad = 0x8000, simkey = seed, and
+ *   (a, b, c, d) = (x[k] N) >> 32 for its words k = 0 .. 3.  A draw whose four values are not distinct
+ *   is passed over without counting as an attempt (the reference's recursion).  The partition
+ *   searches and the surrogates use quads below 24, the shuffles below 0x4000 .. 0x410f: the streams
+ *   of one seed do not meet.
+ *
+ * wc_graph_rewire: randmio_und_signed.
+ *     wr [B][R][N][N]  the matrix after the run, its weights moved with their signs; diagonal 0
+ *
+ * wc_graph_null_model: null_model_und_sign.  The matrix is rewired as above where fewer than
+ *   N (N - 1) off-diagonal entries are positive (:2268); else eff = 0 and no draw is consumed.  Of
+ *   the rewired matrix only the signs are used.  Then, once per sign s, the positive first
+ *   (pass 0, 1): Acur and A_rcur the sign-s entries of w and of the rewired matrix;
+ *     S   [N]  the column sums of w Acur, in ascending row order;
+ *     Wv       the sign-s weights of the strict upper triangle of w, sorted ascending, wsize of them;
+ *     the live list: the sign-s places (i, j), i < j, of the rewired matrix, row-major; wsize too;
+ *     P[i][j] = S[i] S[j].
+ *   neg_mode says what the negative pass takes for w: 0, the reference's code as written, takes w
+ *   itself, so S and Wv are negative, Wv begins with the largest magnitude, and the value written,
+ *   -Wv, is POSITIVE: on a matrix with negative weights the reference returns a w0 without any, and
+ *   r[1] = NaN.  This is the reference's behaviour, pinned to its own outputs, not the definition.
+ *   1, the definition (BCT's null_model_und_sign.m), takes -w: S and Wv positive, the value written,
+ *   -Wv, negative.  The positive pass does not depend on it.
+ *   period = round(1 / wei_freq), 0 .. 64 (more: WC_EUNSUPPORTED).  period 0 (wei_freq 0): one sort,
+ *   the place of rank x receives Wv[x].  Else for m = wsize, wsize - period, ... while m > 0, period
+ *   number p = 0, 1, ...:
+ *     1. Oind: the m live places ordered by (P[i][j], place in the live list), < on the doubles, -0.0
+ *        equal to 0.0: np.argsort's result wherever no two live keys are equal, the stable one else;
+ *     2. R[0 .. k), k = min(m, period): the first k values of a Fisher-Yates shuffle of 0 .. m-1:
+ *        for q = 0 .. k-1, j = q + ((word_q (m - q)) >> 32), swap places q and j, R[q] = place q;
+ *        word_q is word q & 3 of the Philox block with step = p, quad = 0x4000 + 0x100 pass + (q >> 2);
+ *     3. for q in order, with o = Oind[R[q]] at (i, j) and v = Wv[R[q]]: w0[i][j] = w0[j][i] = v in
+ *        pass 0, -v in pass 1; fi = 1 - v / S[i], fj = 1 - v / S[j]; P[i][:] *= fi, then P[:][i] *= fi
+ *        (P[i][i] twice), then the same with j and fj (P[i][j] takes fi before fj); S[i] -= v,
+ *        S[j] -= v.  One rounding per operation, no fma;
+ *     4. the k places leave the live list and the k weights leave Wv, the order of the rest kept.
+ *   S[i] or S[j] equal to 0 at step 3 (the reference divides by zero): the run stops with status 1,
+ *   w0 and r NaN, eff and draws as counted.
+ *     w0 [B][R][N][N]  the null model, symmetric, diagonal 0
+ *     r  [B][R][2]     the Pearson correlation of the positive strengths of w and of w0 (column sums
+ *                      of the positive entries), and of the negative ones; clipped to [-1, 1]; NaN
+ *                      where a sequence is constant (0 / 0, as np.corrcoef).  May be NULL.
+ *
+ * Both: a matrix with a NaN or an infinity anywhere, the diagonal included, has status 3; else one
+ * with w[i][j] != w[j][i] somewhere has status 2; wr, w0 and r are NaN and eff and draws 0 in all its
+ * runs, and no other matrix is affected.
+ * Workspace: the sorted weights lie in global memory, one slot of wc_graph_null_model_slot_bytes(N) =
+ * 4 N (N - 1) bytes per workgroup (0 for an N outside 4 .. 96); the grid is min(B R, ws_bytes / slot)
+ * workgroups, which stride over the problems; wc_graph_rewire takes the same workspace.  ws_bytes
+ * below one slot: WC_EINVAL.  Fixed order, no atomics: a (matrix, seed) pair gives the same bits
+ * alone, in any batch and with any ws_bytes.
+ * Checked before any device work: B, R >= 1, 4 <= N <= 96 (less: WC_EINVAL, four distinct nodes do
+ * not exist; more: WC_EUNSUPPORTED), B R < 2^31, bin_swaps >= 0 and itr A < 2^31, period and neg_mode
+ * in range; w, seeds, wr or w0 and the workspace not NULL; fp64 and uint64 arrays and the workspace
+ * 8-byte, info 4-byte aligned; no output, the used part of the workspace included, overlapping an
+ * input or another output. */
+size_t wc_graph_null_model_slot_bytes(int N);
+int wc_graph_rewire(int B, int R, int N, const double* w, int bin_swaps, const uint64_t* seeds,
+                    double* wr, int32_t* info, void* workspace, size_t ws_bytes, void* stream);
+int wc_graph_null_model(int B, int R, int N, const double* w, int bin_swaps, int period, int neg_mode,
+                        const uint64_t* seeds, double* w0, double* r, int32_t* info,
+                        void* workspace, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -110,6 +110,10 @@ _SIGNATURES = {
     "wc_state_stats": (c_int, [c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "wc_surrogate_fc": (c_int, [c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp]),
     "wc_surrogate_test": (c_int, [c_int, c_int, c_int, c_vp, c_vp, c_dbl, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "wc_graph_null_model_slot_bytes": (c_sz, [c_int]),
+    "wc_graph_rewire": (c_int, [c_int, c_int, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "wc_graph_null_model": (c_int, [c_int, c_int, c_int, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz,
+                                    c_vp]),
 }
 
 

@@ -13,7 +13,9 @@ partition); community_louvain, agreement and get_agreement_matrix through
 sigchain.graph_louvain, graph_agreement and graph_consensus_matrix;
 modularity_louvain_und_sign and consensus_und through partition (partition_np);
 probabilistic_thresholding, the surrogate test that decides which FC entries are
-links at all, through surrogate.fc_surrogate_test (surrogate_np).  torch and
+links at all, through surrogate.fc_surrogate_test (surrogate_np);
+randmio_und_signed, null_model_und_sign and participation_coef_norm through
+nullmodel (nullmodel_np).  torch and
 the library are imported on first use, so importing this module stays light.
 
 Outside: of the partition search the 'negative_sym' and 'negative_asym'
@@ -21,11 +23,12 @@ objectives (unreachable in the reference, which refuses negative weights
 first), the spectral search of modularity_und (its kci form is
 graph_module_measures' Q), and N > 96; probabilistic_thresholding2, the
 rank-remapped variant of the surrogate test.  The rest of the 2,600-line
-toolbox (rich club, assortativity, null-model variants) is analysis outside the
-sweep path.
+toolbox (rich club, assortativity, the other null models) is analysis outside
+the sweep path.
 """
 import numpy as np
 
+from .nullmodel_np import null_model_und_sign, participation_coef_norm, randmio_und_signed  # noqa: F401  (wc_nullmodel.hip)
 from .partition_np import consensus_und, modularity_louvain_und_sign  # noqa: F401  (wc_louvain_sign.hip)
 from .surrogate_np import probabilistic_thresholding  # noqa: F401  (wc_surrogate.hip)
 
