@@ -1,7 +1,8 @@
-"""What the wrappers of sigchain, utils and graph_utils do to their arguments before and after a library
-call, once: the tensor gate, the [B] axis a single matrix or series lacks, measure names, workspaces.
-Plain functions; every message is the caller's own sentence, passed in.
+"""What the wrappers do to their arguments before and after a library call, once: the tensor and number
+gates, the [B] axis a single matrix or series lacks, measure names, workspaces, a seeded run's seeds and
+[R] axis.  Plain functions; every message is the caller's own sentence, passed in.
 """
+import numpy as np
 import torch
 
 
@@ -13,6 +14,20 @@ def tensor(name, what, t, dtype, dims=None, last=None, shapes=None, device=None)
     if not ok or (device is not None and t.device != device):
         raise TypeError(f"{name}: {what}")
     return t
+
+
+def integer(name, what, x, lo=None):
+    """int(x) of a Python or numpy integer, no bool, at least lo where given; else ValueError(f"{name}: {what}")."""
+    if isinstance(x, bool) or not isinstance(x, (int, np.integer)) or (lo is not None and x < lo):
+        raise ValueError(f"{name}: {what}")
+    return int(x)
+
+
+def real(name, what, x, ok=None):
+    """x, a Python or numpy integer or float, no bool, with ok(x) where given; else ValueError(f"{name}: {what}")."""
+    if isinstance(x, bool) or not isinstance(x, (int, float, np.integer, np.floating)) or not (ok is None or ok(x)):
+        raise ValueError(f"{name}: {what}")
+    return x
 
 
 def stack(name, what, t, dtype=torch.float64, ndim=3, batch=0, last=None, square=False):
@@ -57,3 +72,36 @@ def ws_default(need, want, cap):
 def workspace(nbytes, device):
     """An fp64 device buffer of at least nbytes, never empty (the library refuses a NULL workspace)."""
     return torch.empty(max((nbytes + 7) // 8, 1), dtype=torch.float64, device=device)
+
+
+def slot_ws_bytes(name, what, ws_bytes, slot, want, cap):
+    """ws_bytes of a workspace of slots (or slabs): None is ws_default, else an int of at least one slot."""
+    return ws_default(slot, want, cap) if ws_bytes is None else integer(name, what, ws_bytes, slot)
+
+
+def seeds(name, given):
+    """(host uint64 array [R], scalar) of an int or a non-empty sequence of ints in [0, 2^64)."""
+    scalar = isinstance(given, (int, np.integer)) and not isinstance(given, bool)
+    vals = [given] if scalar else (list(given) if isinstance(given, (list, tuple, range, np.ndarray)) else None)
+    if not vals or any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) < 1 << 64
+                       for v in vals):
+        raise ValueError(f"{name}: seeds must be an int or a non-empty sequence of ints in [0, 2^64), got {given!r}")
+    return np.array([int(v) for v in vals], dtype=np.uint64), scalar
+
+
+def seed_list(name, what, given, count, first=0):
+    """Host uint64 array of count seeds, first .. first + count - 1 for None; else ValueError(f"{name}: {what}")."""
+    arr, scalar = seeds(name, range(first, first + count) if given is None else given)
+    if scalar or len(arr) != count:
+        raise ValueError(f"{name}: {what}")
+    return arr
+
+
+def upload_seeds(arr, device):
+    """The uint64 seeds on the device, as the int64 tensor of the same bits (torch has no uint64 arithmetic)."""
+    return torch.from_numpy(arr.view(np.int64)).to(device)
+
+
+def unrun(scalar, single, res):
+    """A tuple of [B][R]... tensors without the R axis for a scalar seed and without the B axis where single."""
+    return unbatch(single, tuple(t[:, 0] for t in res) if scalar else res)

@@ -1,6 +1,7 @@
 // wc_args.h -- how an entry point refuses bad arguments, before any device work (host code only;
 // included from wc_common.h).  wc_graph_louvain (wc_louvain.hip) is the example to copy: shapes,
-// NULL pointers, then one table of input spans and one of output spans through wc_check_spans.
+// NULL pointers, then one table of input spans and one of output spans through wc_check_spans;
+// wc_graph_louvain_sign (wc_louvain_sign.hip) for a seeded entry with a workspace of slots.
 #pragma once
 #include <stdarg.h>
 #include <stdint.h>
@@ -61,6 +62,38 @@ inline int wc_check_spans(const char* fn, const WcSpan* ins, int nins, const WcS
     if (int rc = wc_check_align(fn, outs, nouts)) return rc;
     if (int rc = wc_check_alias(fn, outs, nouts, ins, nins)) return rc;
     return wc_check_disjoint(fn, outs, nouts);
+}
+
+// a seeded batch, B matrices times R seeds, a run each: B >= 1, R >= 1, N in [nmin, nmax], B R < 2^31, in
+// that order.  The caller's clauses: why nmin (nullptr: the bare "N < nmin"), why nmax, and what B R
+// counts (nullptr: no bound on it).
+inline int wc_check_seeded(const char* fn, int B, int R, int N, int nmin, const char* nmin_why, int nmax,
+                           const char* nmax_why, const char* runs) {
+    if (B < 1) return wc_fail(WC_EINVAL, "%s: B < 1", fn);
+    if (R < 1) return wc_fail(WC_EINVAL, "%s: R < 1", fn);
+    if (N < nmin && !nmin_why) return wc_fail(WC_EINVAL, "%s: N < %d", fn, nmin);
+    if (N < nmin) return wc_fail(WC_EINVAL, "%s: N = %d < %d (%s)", fn, N, nmin, nmin_why);
+    if (N > nmax) return wc_fail(WC_EUNSUPPORTED, "%s: N = %d > %d (%s)", fn, N, nmax, nmax_why);
+    if (runs && (int64_t)B * R > INT32_MAX)
+        return wc_fail(WC_EINVAL, "%s: 2^31 %s or more (B times R)", fn, runs);
+    return WC_OK;
+}
+
+// a workspace of one slot per workgroup, the workgroups striding over the runs: min(ws_bytes / slot, runs)
+// slots and the span they cover, for the table of outputs; slot_what is the slot's formula, as "16 N^2"
+struct WcSlots {
+    size_t slots;
+    WcSpan span;
+};
+
+inline int wc_plan_slots(const char* fn, const void* workspace, size_t ws_bytes, size_t slot, const char* slot_what,
+                         size_t runs, WcSlots* plan) {
+    if (ws_bytes < slot)
+        return wc_fail(WC_EINVAL, "%s: ws_bytes = %zu is less than one slot of %s = %zu bytes", fn, ws_bytes, slot_what,
+                       slot);
+    plan->slots = ws_bytes / slot < runs ? ws_bytes / slot : runs;
+    plan->span = {"workspace", workspace, plan->slots * slot, 8};
+    return WC_OK;
 }
 
 // size_fn names the query that returns need

@@ -223,14 +223,7 @@ __global__ void __launch_bounds__(kAgThreads) agreement_kernel(int R, int N, con
     }
 }
 
-// ---- argument checks ----
-int check_shape(const char* fn, int B, int R, int N) {
-    if (B < 1) return wc_fail(WC_EINVAL, "%s: B < 1", fn);
-    if (R < 1) return wc_fail(WC_EINVAL, "%s: R < 1", fn);
-    if (N < 2) return wc_fail(WC_EINVAL, "%s: N < 2", fn);
-    if (N > kMaxN) return wc_fail(WC_EUNSUPPORTED, "%s: N = %d > 96 (one matrix per workgroup, in LDS)", fn, N);
-    return WC_OK;
-}
+const char* const kWhyMaxN = "one matrix per workgroup, in LDS";
 
 }  // namespace
 
@@ -240,8 +233,7 @@ int wc_graph_louvain(int B, int R, int N, const double* obj, const double* norm,
                      const uint64_t* seeds, int32_t* ci, double* q, int32_t* info, void* stream) {
     wc_clear_err();
     const char* fn = "wc_graph_louvain";
-    if (int rc = check_shape(fn, B, R, N)) return rc;
-    if ((int64_t)B * R > INT32_MAX) return wc_fail(WC_EINVAL, "wc_graph_louvain: 2^31 workgroups or more (B times R)");
+    if (int rc = wc_check_seeded(fn, B, R, N, 2, nullptr, kMaxN, kWhyMaxN, "workgroups")) return rc;
     if (!obj || !norm || !seeds || !ci || !q)
         return wc_fail(WC_EINVAL, "wc_graph_louvain: obj, norm, seeds, ci or q is NULL");
     const size_t b = B, r = R, n = N;
@@ -259,7 +251,7 @@ int wc_graph_louvain(int B, int R, int N, const double* obj, const double* norm,
 int wc_graph_agreement(int B, int R, int N, const int32_t* ci, double* D, void* stream) {
     wc_clear_err();
     const char* fn = "wc_graph_agreement";
-    if (int rc = check_shape(fn, B, R, N)) return rc;
+    if (int rc = wc_check_seeded(fn, B, R, N, 2, nullptr, kMaxN, kWhyMaxN, nullptr)) return rc;  // the grid is B
     if (!ci || !D) return wc_fail(WC_EINVAL, "wc_graph_agreement: ci or D is NULL");
     const size_t b = B, r = R, n = N;
     const WcSpan ins[1] = {{"ci", ci, b * r * n * 4, 4}};

@@ -264,28 +264,23 @@ int wc_graph_louvain_sign(int B, int R, int N, const double* w, double gamma, in
                           int32_t* ci, double* q, int32_t* info, void* workspace, size_t ws_bytes, void* stream) {
     wc_clear_err();
     const char* fn = "wc_graph_louvain_sign";
-    if (B < 1) return wc_fail(WC_EINVAL, "%s: B < 1", fn);
-    if (R < 1) return wc_fail(WC_EINVAL, "%s: R < 1", fn);
-    if (N < 2) return wc_fail(WC_EINVAL, "%s: N < 2", fn);
-    if (N > kMaxN)
-        return wc_fail(WC_EUNSUPPORTED, "%s: N = %d > 96 (the node-to-module degrees of one matrix per workgroup, in LDS)",
-                       fn, N);
-    if ((int64_t)B * R > INT32_MAX) return wc_fail(WC_EINVAL, "%s: 2^31 problems or more (B times R)", fn);
+    if (int rc = wc_check_seeded(fn, B, R, N, 2, nullptr, kMaxN,
+                                 "the node-to-module degrees of one matrix per workgroup, in LDS", "problems"))
+        return rc;
     if (qtype < 0 || qtype > 4) return wc_fail(WC_EINVAL, "%s: qtype = %d, must be 0 .. 4 (sta, pos, smp, gja, neg)", fn, qtype);
     if (!isfinite(gamma)) return wc_fail(WC_EINVAL, "%s: gamma is not finite", fn);
     if (!w || !seeds || !ci || !q || !workspace)
         return wc_fail(WC_EINVAL, "%s: w, seeds, ci, q or workspace is NULL", fn);
-    const size_t b = B, r = R, n = N, slot = 2 * n * n * sizeof(double);
-    if (ws_bytes < slot)
-        return wc_fail(WC_EINVAL, "%s: ws_bytes = %zu is less than one slot of 16 N^2 = %zu bytes", fn, ws_bytes, slot);
-    const size_t probs = b * r, slots = ws_bytes / slot < probs ? ws_bytes / slot : probs;
+    const size_t b = B, r = R, n = N, probs = b * r;
+    WcSlots plan;
+    if (int rc = wc_plan_slots(fn, workspace, ws_bytes, 2 * n * n * sizeof(double), "16 N^2", probs, &plan)) return rc;
     const WcSpan ins[2] = {{"w", w, b * n * n * 8, 8}, {"seeds", seeds, r * 8, 8}};
     const WcSpan outs[4] = {{"ci", ci, b * r * n * 4, 4}, {"q", q, b * r * 8, 8}, {"info", info, b * r * 2 * 4, 4},
-                            {"workspace", workspace, slots * slot, 8}};
+                            plan.span};
     if (int rc = wc_check_spans(fn, ins, 2, outs, 4)) return rc;
     const size_t lds = lds_bytes(N);
     if (int rc = wc_raise_lds(fn, louvain_sign_kernel, lds)) return rc;
-    hipLaunchKernelGGL(louvain_sign_kernel, dim3((unsigned)slots), dim3(kWave), lds, static_cast<hipStream_t>(stream),
+    hipLaunchKernelGGL(louvain_sign_kernel, dim3((unsigned)plan.slots), dim3(kWave), lds, static_cast<hipStream_t>(stream),
                        (int)probs, R, N, w, gamma, qtype, seeds, ci, q, info, static_cast<double*>(workspace));
     return wc_hip_check(fn);
 }

@@ -478,12 +478,9 @@ int run(const char* fn, bool rewire_only, int B, int R, int N, const double* w, 
         const uint64_t* seeds, double* out, const char* out_name, double* r, int32_t* info, void* workspace,
         size_t ws_bytes, void* stream) {
     wc_clear_err();
-    if (B < 1) return wc_fail(WC_EINVAL, "%s: B < 1", fn);
-    if (R < 1) return wc_fail(WC_EINVAL, "%s: R < 1", fn);
-    if (N < 4) return wc_fail(WC_EINVAL, "%s: N = %d < 4 (a rewiring takes four distinct nodes)", fn, N);
-    if (N > kMaxN)
-        return wc_fail(WC_EUNSUPPORTED, "%s: N = %d > 96 (one matrix per workgroup, in LDS)", fn, N);
-    if ((int64_t)B * R > INT32_MAX) return wc_fail(WC_EINVAL, "%s: 2^31 problems or more (B times R)", fn);
+    if (int rc = wc_check_seeded(fn, B, R, N, 4, "a rewiring takes four distinct nodes", kMaxN,
+                                 "one matrix per workgroup, in LDS", "problems"))
+        return rc;
     if (bin_swaps < 0) return wc_fail(WC_EINVAL, "%s: bin_swaps = %d < 0", fn, bin_swaps);
     const int64_t itr = (int64_t)bin_swaps * (N * (N - 1) / 2);
     const int half = (N & 1) ? ((((N - 1) / 2) & 1) ? (N + 1) / 2 : (N - 1) / 2) : N / 2;
@@ -499,17 +496,16 @@ int run(const char* fn, bool rewire_only, int B, int R, int N, const double* w, 
     }
     if (!w || !seeds || !out || !workspace)
         return wc_fail(WC_EINVAL, "%s: w, seeds, %s or workspace is NULL", fn, out_name);
-    const size_t b = B, rr = R, n = N, slot = slot_bytes(N);
-    if (ws_bytes < slot)
-        return wc_fail(WC_EINVAL, "%s: ws_bytes = %zu is less than one slot of 4 N (N - 1) = %zu bytes", fn, ws_bytes, slot);
-    const size_t probs = b * rr, slots = ws_bytes / slot < probs ? ws_bytes / slot : probs;
+    const size_t b = B, rr = R, n = N, probs = b * rr;
+    WcSlots plan;
+    if (int rc = wc_plan_slots(fn, workspace, ws_bytes, slot_bytes(N), "4 N (N - 1)", probs, &plan)) return rc;
     const WcSpan ins[2] = {{"w", w, b * n * n * 8, 8}, {"seeds", seeds, rr * 8, 8}};
     const WcSpan outs[4] = {{out_name, out, probs * n * n * 8, 8}, {"r", r, probs * 2 * 8, 8},
-                            {"info", info, probs * 3 * 4, 4}, {"workspace", workspace, slots * slot, 8}};
+                            {"info", info, probs * 3 * 4, 4}, plan.span};
     if (int rc = wc_check_spans(fn, ins, 2, outs, 4)) return rc;
     const size_t lds = lds_bytes(N);
     if (int rc = wc_raise_lds(fn, nullmodel_kernel, lds)) return rc;
-    hipLaunchKernelGGL(nullmodel_kernel, dim3((unsigned)slots), dim3(kThreads), lds, static_cast<hipStream_t>(stream),
+    hipLaunchKernelGGL(nullmodel_kernel, dim3((unsigned)plan.slots), dim3(kThreads), lds, static_cast<hipStream_t>(stream),
                        (int)probs, R, N, w, (int)itr, period, neg_mode, rewire_only ? 1 : 0, seeds, out, r, info,
                        static_cast<double*>(workspace));
     return wc_hip_check(fn);

@@ -32,28 +32,22 @@ def _stack(name, w):
 
 
 def _swaps(name, bin_swaps, N):
-    if isinstance(bin_swaps, bool) or not isinstance(bin_swaps, (int, np.integer)) or bin_swaps < 0:
-        raise ValueError(f"{name}: bin_swaps = {bin_swaps!r}, must be an int >= 0")
+    bin_swaps = _args.integer(name, f"bin_swaps = {bin_swaps!r}, must be an int >= 0", bin_swaps, 0)
     attempts = int(np.round(N / 2)) + 1
-    if int(bin_swaps) * (N * (N - 1) // 2) * attempts >= 1 << 31:
+    if bin_swaps * (N * (N - 1) // 2) * attempts >= 1 << 31:
         raise ValueError(f"{name}: bin_swaps = {bin_swaps}: its iterations times {attempts} attempts reach 2^31")
-    return int(bin_swaps)
+    return bin_swaps
 
 
 def _ws_bytes(name, ws_bytes, N, runs):
     slot = null_model_slot_bytes(N)
-    if ws_bytes is None:
-        return _args.ws_default(slot, runs * slot, NULL_MODEL_SLOTS * slot)
-    if isinstance(ws_bytes, bool) or not isinstance(ws_bytes, (int, np.integer)) or ws_bytes < slot:
-        raise ValueError(f"{name}: ws_bytes = {ws_bytes!r}, needs at least one slot of 4 N (N - 1) = {slot} bytes")
-    return int(ws_bytes)
+    return _args.slot_ws_bytes(name, f"ws_bytes = {ws_bytes!r}, needs at least one slot of 4 N (N - 1) = {slot} bytes",
+                               ws_bytes, slot, runs * slot, NULL_MODEL_SLOTS * slot)
 
 
 def period_of(name, wei_freq):
     """round(1 / wei_freq) as the reference takes it (np.round; graph_utils.py:2297), 0 for wei_freq 0."""
-    if isinstance(wei_freq, bool) or not isinstance(wei_freq, (int, float, np.integer, np.floating)) \
-            or not 0 <= wei_freq <= 1:
-        raise ValueError(f"{name}: wei_freq = {wei_freq!r}, must be a number in [0, 1]")
+    _args.real(name, f"wei_freq = {wei_freq!r}, must be a number in [0, 1]", wei_freq, lambda f: 0 <= f <= 1)
     if wei_freq == 0:
         return 0
     period = int(np.round(1 / wei_freq))
@@ -77,23 +71,19 @@ def graph_rewire(w, bin_swaps=5, seeds=0, want_info=False, ws_bytes=None):
     with a NaN or inf (status 3) or that is not symmetric (status 2) has wr NaN and 0 rewirings.
     ws_bytes as graph_null_model's."""
     name = "graph_rewire"
-    seed_arr, scalar = sigchain._louvain_seeds(name, seeds)
+    seed_arr, scalar = _args.seeds(name, seeds)
     w, single, B, N = _stack(name, w)
     bin_swaps = _swaps(name, bin_swaps, N)
     R = len(seed_arr)
     ws_bytes = _ws_bytes(name, ws_bytes, N, B * R)
     dev = w.device
-    ws = _args.workspace(ws_bytes, dev)
-    seeds_dev = torch.from_numpy(seed_arr.view(np.int64)).to(dev)
+    ws, seeds_dev = _args.workspace(ws_bytes, dev), _args.upload_seeds(seed_arr, dev)
     wr = torch.empty((B, R, N, N), dtype=torch.float64, device=dev)
     info = torch.empty((B, R, 3), dtype=torch.int32, device=dev) if want_info else None
     _lib.check(_lib.lib().wc_graph_rewire(B, R, N, _lib.ptr(w), bin_swaps, _lib.ptr(seeds_dev), _lib.ptr(wr),
                                           _lib.ptr(info), _lib.ptr(ws), ws_bytes, _lib.stream_handle()),
                "wc_graph_rewire")
-    res = (wr, info) if want_info else (wr,)
-    if scalar:
-        res = tuple(t[:, 0] for t in res)
-    res = _args.unbatch(single, res)
+    res = _args.unrun(scalar, single, (wr, info) if want_info else (wr,))
     return res if want_info else res[0]
 
 
@@ -126,14 +116,13 @@ def graph_null_model(w, seeds=0, bin_swaps=5, wei_freq=0.1, negative="bct", want
     if not isinstance(negative, str) or negative not in NEGATIVE_MODES:
         raise ValueError(f"{name}: negative = {negative!r}, must be one of {list(NEGATIVE_MODES)}")
     period = period_of(name, wei_freq)
-    seed_arr, scalar = sigchain._louvain_seeds(name, seeds)
+    seed_arr, scalar = _args.seeds(name, seeds)
     w, single, B, N = _stack(name, w)
     bin_swaps = _swaps(name, bin_swaps, N)
     R = len(seed_arr)
     ws_bytes = _ws_bytes(name, ws_bytes, N, B * R)
     dev = w.device
-    ws = _args.workspace(ws_bytes, dev)
-    seeds_dev = torch.from_numpy(seed_arr.view(np.int64)).to(dev)
+    ws, seeds_dev = _args.workspace(ws_bytes, dev), _args.upload_seeds(seed_arr, dev)
     w0 = torch.empty((B, R, N, N), dtype=torch.float64, device=dev)
     r = torch.empty((B, R, 2), dtype=torch.float64, device=dev) if want_stats else None
     info = torch.empty((B, R, 3), dtype=torch.int32, device=dev) if want_stats else None
@@ -141,10 +130,7 @@ def graph_null_model(w, seeds=0, bin_swaps=5, wei_freq=0.1, negative="bct", want
                                               _lib.ptr(seeds_dev), _lib.ptr(w0), _lib.ptr(r), _lib.ptr(info),
                                               _lib.ptr(ws), ws_bytes, _lib.stream_handle()),
                "wc_graph_null_model")
-    res = (w0, r, info) if want_stats else (w0,)
-    if scalar:
-        res = tuple(t[:, 0] for t in res)
-    res = _args.unbatch(single, res)
+    res = _args.unrun(scalar, single, (w0, r, info) if want_stats else (w0,))
     return res if want_stats else res[0]
 
 
@@ -176,14 +162,9 @@ def participation_norm(w, ci, reps=100, seeds=None, bin_swaps=5, wei_freq=0.1, n
     the result is the same bits for any max_bytes.  A matrix of which any run has a non-zero status
     (graph_null_model) has NaN in its rows of mean and std; one flag per matrix stays on the device."""
     name = "participation_norm"
-    if isinstance(reps, bool) or not isinstance(reps, (int, np.integer)) or reps < 1:
-        raise ValueError(f"{name}: reps = {reps!r}, must be a positive int")
-    if isinstance(max_bytes, bool) or not isinstance(max_bytes, (int, np.integer)) or max_bytes < 1:
-        raise ValueError(f"{name}: max_bytes = {max_bytes!r}, must be a positive int")
-    reps = int(reps)
-    base, scalar = sigchain._louvain_seeds(name, range(reps) if seeds is None else seeds)
-    if scalar or len(base) != reps:
-        raise ValueError(f"{name}: seeds must be a sequence of length reps = {reps}, or None")
+    reps = _args.integer(name, f"reps = {reps!r}, must be a positive int", reps, 1)
+    max_bytes = _args.integer(name, f"max_bytes = {max_bytes!r}, must be a positive int", max_bytes, 1)
+    base = _args.seed_list(name, f"seeds must be a sequence of length reps = {reps}, or None", seeds, reps)
     if not isinstance(negative, str) or negative not in NEGATIVE_MODES:
         raise ValueError(f"{name}: negative = {negative!r}, must be one of {list(NEGATIVE_MODES)}")
     period_of(name, wei_freq)
@@ -196,7 +177,7 @@ def participation_norm(w, ci, reps=100, seeds=None, bin_swaps=5, wei_freq=0.1, n
     w = w.reshape(B, N, N)
     ko = sigchain._halving_sum(w)                                              # [B][N]
     km = _module_strengths(w, onehot)                                          # [B][N][K]
-    chunk = max(1, min(reps, int(max_bytes) // (8 * B * N * N)))
+    chunk = max(1, min(reps, max_bytes // (8 * B * N * N)))
     p_all = torch.empty((B, reps, N), dtype=torch.float64, device=dev)
     bad = torch.zeros((B,), dtype=torch.bool, device=dev)
     for r0 in range(0, reps, chunk):

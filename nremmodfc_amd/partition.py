@@ -7,7 +7,6 @@ Device tensors in and out; partition_np holds the numpy facades that graph_utils
 """
 import math
 
-import numpy as np
 import torch
 
 from . import _args, _lib, sigchain
@@ -45,30 +44,22 @@ def graph_louvain_sign(w, seeds=0, gamma=1.0, qtype="sta", want_info=False, ws_b
     name = "graph_louvain_sign"
     if not isinstance(qtype, str) or qtype not in LOUVAIN_SIGN_QTYPES:
         raise ValueError(f"{name}: modularity type unknown: qtype {qtype!r}, must be one of {list(LOUVAIN_SIGN_QTYPES)}")
-    if isinstance(gamma, bool) or not isinstance(gamma, (int, float, np.integer, np.floating)) \
-            or not math.isfinite(gamma):
-        raise ValueError(f"{name}: gamma = {gamma!r}, must be a finite number")
-    seed_arr, scalar = sigchain._louvain_seeds(name, seeds)
+    _args.real(name, f"gamma = {gamma!r}, must be a finite number", gamma, math.isfinite)
+    seed_arr, scalar = _args.seeds(name, seeds)
     w, single, B, N = sigchain._graph_stack(name, w)
     R, slot = len(seed_arr), louvain_sign_slot_bytes(N)
-    if ws_bytes is None:
-        ws_bytes = _args.ws_default(slot, B * R * slot, LOUVAIN_SIGN_SLOTS * slot)
-    elif isinstance(ws_bytes, bool) or not isinstance(ws_bytes, (int, np.integer)) or ws_bytes < slot:
-        raise ValueError(f"{name}: ws_bytes = {ws_bytes!r}, needs at least one slot of 16 N^2 = {slot} bytes")
+    ws_bytes = _args.slot_ws_bytes(name, f"ws_bytes = {ws_bytes!r}, needs at least one slot of 16 N^2 = {slot} bytes",
+                                   ws_bytes, slot, B * R * slot, LOUVAIN_SIGN_SLOTS * slot)
     dev = w.device
-    ws = _args.workspace(int(ws_bytes), dev)
-    seeds_dev = torch.from_numpy(seed_arr.view(np.int64)).to(dev)
+    ws, seeds_dev = _args.workspace(ws_bytes, dev), _args.upload_seeds(seed_arr, dev)
     out = torch.empty((B, R, N), dtype=torch.int32, device=dev)
     q = torch.empty((B, R), dtype=torch.float64, device=dev)
     info = torch.empty((B, R, 2), dtype=torch.int32, device=dev) if want_info else None
     _lib.check(_lib.lib().wc_graph_louvain_sign(B, R, N, _lib.ptr(w), float(gamma), LOUVAIN_SIGN_QTYPES.index(qtype),
                                                 _lib.ptr(seeds_dev), _lib.ptr(out), _lib.ptr(q), _lib.ptr(info),
-                                                _lib.ptr(ws), int(ws_bytes), _lib.stream_handle()),
+                                                _lib.ptr(ws), ws_bytes, _lib.stream_handle()),
                "wc_graph_louvain_sign")
-    res = (out, q) + ((info,) if want_info else ())
-    if scalar:
-        res = tuple(t[:, 0] for t in res)
-    return _args.unbatch(single, res)
+    return _args.unrun(scalar, single, (out, q) + ((info,) if want_info else ()))
 
 
 def _first_occurrence(ci):
@@ -98,26 +89,18 @@ def graph_consensus(D, tau, reps=1000, seeds=None, max_iter=100):
     has neither a cap nor a refusal: it loops until convergence and raises from the search.  Its
     branch for a dt without zeros cannot be taken, the diagonal being zero, and is left out."""
     name = "graph_consensus"
-    if isinstance(reps, bool) or not isinstance(reps, (int, np.integer)) or reps < 1:
-        raise ValueError(f"{name}: reps = {reps!r}, must be a positive int")
-    if isinstance(max_iter, bool) or not isinstance(max_iter, (int, np.integer)) or max_iter < 1:
-        raise ValueError(f"{name}: max_iter = {max_iter!r}, must be a positive int")
-    if isinstance(tau, bool) or not isinstance(tau, (int, float, np.integer, np.floating)) or not math.isfinite(tau):
-        raise ValueError(f"{name}: tau = {tau!r}, must be a finite number")
-    reps = int(reps)
-    if seeds is None:
-        seeds = range(reps)
-    base, scalar = sigchain._louvain_seeds(name, seeds)
-    if scalar or len(base) != reps:
-        raise ValueError(f"{name}: seeds must be a sequence of length reps = {reps}, or None")
+    reps = _args.integer(name, f"reps = {reps!r}, must be a positive int", reps, 1)
+    max_iter = _args.integer(name, f"max_iter = {max_iter!r}, must be a positive int", max_iter, 1)
+    _args.real(name, f"tau = {tau!r}, must be a finite number", tau, math.isfinite)
+    base = _args.seed_list(name, f"seeds must be a sequence of length reps = {reps}, or None", seeds, reps)
     D, single, B, N = sigchain._graph_stack(name, D)
     dev = D.device
     ci = torch.full((B, N), -1, dtype=torch.int32, device=dev)
-    iters = torch.full((B,), int(max_iter), dtype=torch.int32, device=dev)
+    iters = torch.full((B,), max_iter, dtype=torch.int32, device=dev)
     open_idx = torch.arange(B, device=dev)
     cur = D.reshape(B, N, N)
     eye = torch.eye(N, dtype=torch.bool, device=dev)
-    for k in range(int(max_iter)):
+    for k in range(max_iter):
         dt = (cur * (cur >= float(tau))).masked_fill(eye, 0.0)        # a NaN stays one, as in the reference
         run_seeds = [(int(s) + k * reps) % (1 << 64) for s in base]
         part, _ = graph_louvain_sign(dt, seeds=run_seeds)

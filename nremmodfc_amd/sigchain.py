@@ -466,16 +466,6 @@ GRAPH_PARTITION_SEARCH = ("graph_louvain", "graph_agreement", "graph_consensus_m
 GRAPH_LOUVAIN_MIN_WEIGHT = -1e-10                     # graph_utils.py:999: anything below is refused
 
 
-def _louvain_seeds(name, seeds):
-    """(host uint64 array [R], scalar) of an int or a sequence of ints in [0, 2^64)."""
-    scalar = isinstance(seeds, (int, np.integer)) and not isinstance(seeds, bool)
-    vals = [seeds] if scalar else (list(seeds) if isinstance(seeds, (list, tuple, range, np.ndarray)) else None)
-    if not vals or any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) < 1 << 64
-                       for v in vals):
-        raise ValueError(f"{name}: seeds must be an int or a non-empty sequence of ints in [0, 2^64), got {seeds!r}")
-    return np.array([int(v) for v in vals], dtype=np.uint64), scalar
-
-
 def _louvain_labels(name, ci, B, N, dev):
     """Starting labels [N] or [B][N] (any integers) -> int32 [B][N] in [0, N), dense in the order of
     the sorted distinct values of each row (np.unique's inverse), on the device and without a sync."""
@@ -537,7 +527,7 @@ def graph_louvain(w, seeds=0, gamma=1.0, ci=None, objective="modularity", want_i
         raise ValueError(f"{name}: objective {objective!r}, must be one of {list(GRAPH_LOUVAIN_OBJECTIVES)} or a "
                          "[N][N] / [B][N][N] fp64 device tensor (negative_sym and negative_asym are not built: "
                          "the reference refuses negative weights before it reaches them)")
-    seed_arr, scalar = _louvain_seeds(name, seeds)
+    seed_arr, scalar = _args.seeds(name, seeds)
     w, single, B, N = _graph_stack(name, w)
     wb = w.reshape(B, N, N)
     dev = w.device
@@ -567,17 +557,14 @@ def graph_louvain(w, seeds=0, gamma=1.0, ci=None, objective="modularity", want_i
         obj = wb - float(gamma) * (wb == 0).to(torch.float64)
     obj = obj.contiguous()
     R = len(seed_arr)
-    seeds_dev = torch.from_numpy(seed_arr.view(np.int64)).to(dev)
+    seeds_dev = _args.upload_seeds(seed_arr, dev)
     out = torch.empty((B, R, N), dtype=torch.int32, device=dev)
     q = torch.empty((B, R), dtype=torch.float64, device=dev)
     info = torch.empty((B, R, 2), dtype=torch.int32, device=dev) if want_info else None
     _lib.check(_lib.lib().wc_graph_louvain(B, R, N, _lib.ptr(obj), _lib.ptr(s), _lib.ptr(ci0), _lib.ptr(seeds_dev),
                                            _lib.ptr(out), _lib.ptr(q), _lib.ptr(info), _lib.stream_handle()),
                "wc_graph_louvain")
-    res = (out, q) + ((info,) if want_info else ())
-    if scalar:
-        res = tuple(t[:, 0] for t in res)
-    return _args.unbatch(single, res)
+    return _args.unrun(scalar, single, (out, q) + ((info,) if want_info else ()))
 
 
 def graph_agreement(ci):
@@ -601,8 +588,7 @@ def graph_consensus_matrix(w, reps=100, tau=0.5, gamma=1.0, ci=None, objective="
     graph_louvain with seeds 0 .. reps-1 (or the reps seeds given), graph_agreement, D / reps, entries
     below tau set to 0, the diagonal 0 -> [B][N][N] or [N][N].  One Louvain launch and one agreement
     launch serve the whole stack.  A matrix that graph_louvain refuses is NaN throughout."""
-    if isinstance(reps, bool) or not isinstance(reps, (int, np.integer)) or reps < 1:
-        raise ValueError(f"graph_consensus_matrix: reps = {reps!r}, must be a positive int")
+    _args.integer("graph_consensus_matrix", f"reps = {reps!r}, must be a positive int", reps, 1)
     if seeds is None:
         seeds = range(int(reps))
     elif isinstance(seeds, (int, np.integer)) or len(seeds) != reps:

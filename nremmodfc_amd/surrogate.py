@@ -6,7 +6,6 @@ made: a surrogate's FC is a normalised Gram product of the rotated spectrum (inc
 
 Device tensors in and out; surrogate_np holds the numpy facade that graph_utils re-exports.
 """
-import numpy as np
 import torch
 
 from . import _args, _lib, sigchain
@@ -33,17 +32,6 @@ def _series(name, x):
         raise ValueError(f"{name}: N = {N}, B = {B}: needs B >= 1 and 2 <= N <= {sigchain.GRAPH_MAX_N} "
                          "(the result feeds the graph kernels)")
     return x.reshape(L, B, N), single, B, N, L
-
-
-def _seeds(name, seeds, S=None):
-    """Host uint64 array of at least two seeds; None: 1 .. S, the reference's np.random.seed(i + 1)."""
-    if seeds is None:
-        seeds = range(1, S + 1)
-    arr, scalar = sigchain._louvain_seeds(name, seeds)
-    if scalar or len(arr) < 2 or (S is not None and len(arr) != S):
-        raise ValueError(f"{name}: seeds must be a sequence of " + (f"surr_number = {S}" if S is not None else "at least 2")
-                         + f" ints in [0, 2^64), got {seeds!r}")
-    return arr
 
 
 def _spectrum(x):
@@ -96,27 +84,23 @@ def surrogate_fc(x, seeds):
     tensor: B S P doubles; fc_surrogate_test walks a large batch in chunks."""
     name = "surrogate_fc"
     x, single, B, N, L = _series(name, x)
-    arr = _seeds(name, seeds)
-    seeds_dev = torch.from_numpy(arr.view(np.int64)).to(x.device)
-    return _args.unbatch(single, _surrogate_fc(x, seeds_dev, len(arr)))
+    arr, scalar = _args.seeds(name, seeds)
+    if scalar or len(arr) < 2:
+        raise ValueError(f"{name}: seeds must be a sequence of at least 2 ints in [0, 2^64), got {seeds!r}")
+    return _args.unbatch(single, _surrogate_fc(x, _args.upload_seeds(arr, x.device), len(arr)))
 
 
 def _test_args(name, x, surr_number, alpha, seeds, ws_bytes):
     """What fc_surrogate_test refuses, before the device is touched -> (x [L][B][N], single, B, N, S, seeds
     uint64 [S], slab bytes, ws_bytes)."""
-    if isinstance(surr_number, bool) or not isinstance(surr_number, (int, np.integer)) or surr_number < 2:
-        raise ValueError(f"{name}: surr_number = {surr_number!r}, must be an int of at least 2")
-    if isinstance(alpha, bool) or not isinstance(alpha, (int, float, np.integer, np.floating)) or not 0 < alpha < 1:
-        raise ValueError(f"{name}: alpha = {alpha!r}, must lie in (0, 1)")
-    S = int(surr_number)
-    arr = _seeds(name, seeds, S)
+    S = _args.integer(name, f"surr_number = {surr_number!r}, must be an int of at least 2", surr_number, 2)
+    _args.real(name, f"alpha = {alpha!r}, must lie in (0, 1)", alpha, lambda a: 0 < a < 1)
+    what = f"seeds must be a sequence of surr_number = {S} ints in [0, 2^64), got {seeds!r}"
+    arr = _args.seed_list(name, what, seeds, S, first=1)        # None: 1 .. S, the reference's np.random.seed(i + 1)
     x, single, B, N, L = _series(name, x)
     slab = surrogate_slab_bytes(N, S)
-    if ws_bytes is None:
-        ws_bytes = _args.ws_default(slab, B * slab, SURROGATE_WS_CAP)
-    elif isinstance(ws_bytes, bool) or not isinstance(ws_bytes, (int, np.integer)) or ws_bytes < slab:
-        raise ValueError(f"{name}: ws_bytes = {ws_bytes!r}, needs at least one simulation's slab of 8 S P = {slab} bytes")
-    return x, single, B, N, S, arr, slab, int(ws_bytes)
+    what = f"ws_bytes = {ws_bytes!r}, needs at least one simulation's slab of 8 S P = {slab} bytes"
+    return x, single, B, N, S, arr, slab, _args.slot_ws_bytes(name, what, ws_bytes, slab, B * slab, SURROGATE_WS_CAP)
 
 
 def fc_surrogate_test(x, surr_number=50, alpha=0.05, seeds=None, want_stats=False, ws_bytes=None):
@@ -139,7 +123,7 @@ def fc_surrogate_test(x, surr_number=50, alpha=0.05, seeds=None, want_stats=Fals
     x, single, B, N, S, arr, slab, ws_bytes = _test_args("fc_surrogate_test", x, surr_number, alpha, seeds, ws_bytes)
     dev, P = x.device, N * (N - 1) // 2
     per = min(B, ws_bytes // slab)
-    seeds_dev = torch.from_numpy(arr.view(np.int64)).to(dev)
+    seeds_dev = _args.upload_seeds(arr, dev)
     fc_adj = torch.empty((B, N, N), dtype=torch.float64, device=dev)
     p_adj = torch.empty((B, N, N), dtype=torch.float64, device=dev)
     stats = {k: torch.empty((B, P), dtype=torch.float64, device=dev) for k in ("mu", "sd", "p")} if want_stats else None

@@ -5,11 +5,19 @@ The expected return codes were recorded from a build of the commit before the en
 wc_args.h (this table run against that library through WCSDE_LIB_OVERRIDE): the shared helpers must
 refuse exactly what the hand-written checks refused, with the same code.  Every row is a call that
 library refuses; "these two may abut" is only ever shown by a later refusal (ws_bytes = 0 giving
-WC_EWORKSPACE), so entries without a workspace have no such rows.
+WC_EWORKSPACE), so entries without a workspace have no such rows.  The seeded entries
+(wc_graph_louvain_sign, wc_graph_rewire, wc_graph_null_model, wc_surrogate_fc, wc_surrogate_test) were
+recorded the same way from the commit before wc_check_seeded and wc_plan_slots.
 
 Per entry: each shape bound; each required pointer NULL; each pointer misaligned by half its alignment;
 each (output, input) and (output, output) pair that the entry checks, overlapping by one element; and
 for a workspace: one byte short, NULL, misaligned, and over each buffer the entry checks it against.
+A workspace of slots has no size function and is refused with WC_EINVAL: it is listed as the last
+output, of min(ws_bytes / slot, runs) slots, with "ws_bytes one byte under one slot" among the shapes.
+
+FIRST: calls to the seeded entries and to wc_graph_louvain and wc_graph_agreement that are wrong in two
+ways, with the code and the whole message of the refusal that comes first: the order of the checks and
+the wording of the clauses that the shared helpers take from their callers.
 """
 import ctypes
 from collections import namedtuple
@@ -83,6 +91,18 @@ def kmeans_shapes(with_ws):
     return rows
 
 
+def seeded_shapes(min_n):
+    """The seeded family (B matrices, R seeds, a run each): B, R, N, and B R just past INT32_MAX."""
+    return [(dict(B=0), EINVAL), (dict(R=0), EINVAL), (dict(N=min_n - 1), EINVAL), (dict(N=97), EUNSUPPORTED),
+            (dict(B=1 << 16, R=1 << 15), EINVAL)]
+
+
+# at N = 90: 4005 iterations a swap, 46 attempts each; 11657 swaps reach 2^31 attempts; N = 4: a slot of 48 bytes
+NULL_MODEL_SWAPS = [(dict(bin_swaps=-1), EINVAL), (dict(bin_swaps=11657), EINVAL), (dict(ws_bytes=32039), EINVAL),
+                    (dict(N=4, ws_bytes=47), EINVAL)]
+SURROGATE_SHAPES = [(dict(B=0), EINVAL), (dict(N=1), EINVAL), (dict(N=97), EUNSUPPORTED), (dict(S=1), EINVAL),
+                    (dict(B=1 << 16, S=1 << 15), EINVAL)]
+
 ENTRIES = [
     entry("wc_graph_louvain",
           dict(B=2, R=3, N=90, obj=P(0), norm=P(1), ci0=P(2), seeds=P(3), ci=P(4), q=P(5), info=P(6)),
@@ -95,6 +115,40 @@ ENTRIES = [
     entry("wc_graph_agreement", dict(B=2, R=3, N=90, ci=P(0), D=P(1)),
           dict(ci=Span("in", 2 * 3 * 90 * 4, 4, 4, True), D=Span("out", 2 * 90 * 90 * 8, 8, 8, True)),
           [(dict(B=0), EINVAL), (dict(R=0), EINVAL), (dict(N=1), EINVAL), (dict(N=97), EUNSUPPORTED)]),
+    entry("wc_graph_louvain_sign",                                   # 6 runs, a slot of 16 N^2 bytes each
+          dict(B=2, R=3, N=90, w=P(0), gamma=1.0, qtype=0, seeds=P(1), ci=P(2), q=P(3), info=P(4), workspace=P(5),
+               ws_bytes=6 * 129600),
+          dict(w=Span("in", 2 * 90 * 90 * 8, 8, 8, True), seeds=Span("in", 3 * 8, 8, 8, True),
+               ci=Span("out", 2 * 3 * 90 * 4, 4, 4, True), q=Span("out", 2 * 3 * 8, 8, 8, True),
+               info=Span("out", 2 * 3 * 2 * 4, 4, 4, False), workspace=Span("out", 6 * 129600, 8, 8, True)),
+          [*seeded_shapes(2), (dict(qtype=5), EINVAL), (dict(qtype=-1), EINVAL), (dict(gamma=INF), EINVAL),
+           (dict(gamma=NAN), EINVAL), (dict(ws_bytes=129599), EINVAL), (dict(N=2, ws_bytes=63), EINVAL)]),
+    entry("wc_graph_rewire",                                         # 6 runs, a slot of 4 N (N - 1) bytes each
+          dict(B=2, R=3, N=90, w=P(0), bin_swaps=5, seeds=P(1), wr=P(2), info=P(3), workspace=P(4), ws_bytes=6 * 32040),
+          dict(w=Span("in", 2 * 90 * 90 * 8, 8, 8, True), seeds=Span("in", 3 * 8, 8, 8, True),
+               wr=Span("out", 6 * 90 * 90 * 8, 8, 8, True), info=Span("out", 6 * 3 * 4, 4, 4, False),
+               workspace=Span("out", 6 * 32040, 8, 8, True)),
+          [*seeded_shapes(4), *NULL_MODEL_SWAPS]),
+    entry("wc_graph_null_model",
+          dict(B=2, R=3, N=90, w=P(0), bin_swaps=5, period=10, neg_mode=1, seeds=P(1), w0=P(2), r=P(3), info=P(4),
+               workspace=P(5), ws_bytes=6 * 32040),
+          dict(w=Span("in", 2 * 90 * 90 * 8, 8, 8, True), seeds=Span("in", 3 * 8, 8, 8, True),
+               w0=Span("out", 6 * 90 * 90 * 8, 8, 8, True), r=Span("out", 6 * 2 * 8, 8, 8, False),
+               info=Span("out", 6 * 3 * 4, 4, 4, False), workspace=Span("out", 6 * 32040, 8, 8, True)),
+          [*seeded_shapes(4), *NULL_MODEL_SWAPS, (dict(period=-1), EINVAL), (dict(period=65), EUNSUPPORTED),
+           (dict(neg_mode=2), EINVAL), (dict(neg_mode=-1), EINVAL)]),
+    entry("wc_surrogate_fc",                                         # 150 bins of 180 columns, P = 4005 pairs
+          dict(B=2, N=90, L=298, S=3, spec=P(0), seeds=P(1), sfc=P(2)),
+          dict(spec=Span("in", 150 * 180 * 16, 16, 16, True), seeds=Span("in", 3 * 8, 8, 8, True),
+               sfc=Span("out", 2 * 3 * 4005 * 8, 8, 8, True)),
+          [*SURROGATE_SHAPES, (dict(L=2), EINVAL), (dict(L=299), EINVAL), (dict(L=4098), EUNSUPPORTED)]),
+    entry("wc_surrogate_test",
+          dict(B=2, N=90, S=3, fc=P(0), sfc=P(1), alpha=0.05, p_adj=P(2), fc_adj=P(3), mu=P(4), sd=P(5), p=P(6)),
+          dict(fc=Span("in", 2 * 90 * 90 * 8, 8, 8, True), sfc=Span("in", 2 * 3 * 4005 * 8, 8, 8, True),
+               p_adj=Span("out", 2 * 90 * 90 * 8, 8, 8, True), fc_adj=Span("out", 2 * 90 * 90 * 8, 8, 8, True),
+               mu=Span("out", 2 * 4005 * 8, 8, 8, False), sd=Span("out", 2 * 4005 * 8, 8, 8, False),
+               p=Span("out", 2 * 4005 * 8, 8, 8, False)),
+          [*SURROGATE_SHAPES, (dict(alpha=0.0), EINVAL), (dict(alpha=1.0), EINVAL), (dict(alpha=NAN), EINVAL)]),
     graph("wc_graph_paths", dict(w=0, lengths=0, include_infinite=1),
           dict(dist=(90 * 90, 8), hops=(90 * 90, 4), stats=(4, 8), ecc=(90, 8))),
     graph("wc_graph_local_efficiency", dict(), dict(eloc=(90, 8)),
@@ -235,3 +289,79 @@ def test_refused_calls_keep_their_codes(e):
         assert msg.startswith(e.fn.encode() + b": "), (e.fn, what, msg)
         if names:
             assert names.encode() in msg, (e.fn, what, msg)
+
+
+BIG = dict(B=1 << 16, R=1 << 15)
+N97 = "N = 97 > 96 (one matrix per workgroup, in LDS)"
+# (entry point, overrides that are wrong in two ways or more, code, the message of the check that fires first)
+FIRST = [
+    ("wc_graph_louvain", dict(B=0, R=0), EINVAL, "B < 1"),
+    ("wc_graph_louvain", dict(R=0, N=97), EINVAL, "R < 1"),
+    ("wc_graph_louvain", dict(N=1, **BIG), EINVAL, "N < 2"),
+    ("wc_graph_louvain", dict(N=97, **BIG), EUNSUPPORTED, N97),
+    ("wc_graph_louvain", dict(obj=None, **BIG), EINVAL, "2^31 workgroups or more (B times R)"),
+    ("wc_graph_louvain", dict(obj=None, seeds=P(3) + 4), EINVAL, "obj, norm, seeds, ci or q is NULL"),
+    ("wc_graph_agreement", dict(B=0, R=0), EINVAL, "B < 1"),
+    ("wc_graph_agreement", dict(R=0, N=97), EINVAL, "R < 1"),
+    ("wc_graph_agreement", dict(N=1, ci=None), EINVAL, "N < 2"),
+    ("wc_graph_agreement", dict(N=97, ci=None), EUNSUPPORTED, N97),
+    ("wc_graph_agreement", dict(ci=None, **BIG), EINVAL, "ci or D is NULL"),          # no bound on B R: a grid of B
+    ("wc_graph_louvain_sign", dict(B=0, R=0), EINVAL, "B < 1"),
+    ("wc_graph_louvain_sign", dict(R=0, N=97), EINVAL, "R < 1"),
+    ("wc_graph_louvain_sign", dict(N=1, **BIG), EINVAL, "N < 2"),
+    ("wc_graph_louvain_sign", dict(N=97, **BIG), EUNSUPPORTED,
+     "N = 97 > 96 (the node-to-module degrees of one matrix per workgroup, in LDS)"),
+    ("wc_graph_louvain_sign", dict(qtype=5, **BIG), EINVAL, "2^31 problems or more (B times R)"),
+    ("wc_graph_louvain_sign", dict(qtype=5, gamma=NAN), EINVAL, "qtype = 5, must be 0 .. 4 (sta, pos, smp, gja, neg)"),
+    ("wc_graph_louvain_sign", dict(gamma=INF, w=None), EINVAL, "gamma is not finite"),
+    ("wc_graph_louvain_sign", dict(workspace=None, ws_bytes=0), EINVAL, "w, seeds, ci, q or workspace is NULL"),
+    ("wc_graph_louvain_sign", dict(ws_bytes=129599, seeds=P(1) + 4), EINVAL,
+     "ws_bytes = 129599 is less than one slot of 16 N^2 = 129600 bytes"),
+    ("wc_graph_louvain_sign", dict(seeds=P(1) + 4, workspace=P(4)), EINVAL, "seeds must be 8-byte aligned"),
+    ("wc_graph_louvain_sign", dict(ws_bytes=129600, workspace=P(4) - 129600 + 8), EINVAL, "workspace must not alias info"),
+    ("wc_graph_rewire", dict(B=0, R=0), EINVAL, "B < 1"),
+    ("wc_graph_rewire", dict(R=0, N=3), EINVAL, "R < 1"),
+    ("wc_graph_rewire", dict(N=3, **BIG), EINVAL, "N = 3 < 4 (a rewiring takes four distinct nodes)"),
+    ("wc_graph_rewire", dict(N=97, **BIG), EUNSUPPORTED, N97),
+    ("wc_graph_rewire", dict(bin_swaps=-1, **BIG), EINVAL, "2^31 problems or more (B times R)"),
+    ("wc_graph_rewire", dict(bin_swaps=-1, w=None), EINVAL, "bin_swaps = -1 < 0"),
+    ("wc_graph_rewire", dict(bin_swaps=11657, w=None), EINVAL,
+     "bin_swaps = 11657: 46686285 iterations of 46 attempts reach 2^31"),
+    ("wc_graph_rewire", dict(wr=None, ws_bytes=0), EINVAL, "w, seeds, wr or workspace is NULL"),
+    ("wc_graph_rewire", dict(ws_bytes=32039, w=P(0) + 4), EINVAL,
+     "ws_bytes = 32039 is less than one slot of 4 N (N - 1) = 32040 bytes"),
+    ("wc_graph_rewire", dict(ws_bytes=32040, workspace=P(2) - 32040 + 8), EINVAL, "workspace must not alias wr"),
+    ("wc_graph_null_model", dict(N=3, **BIG), EINVAL, "N = 3 < 4 (a rewiring takes four distinct nodes)"),
+    ("wc_graph_null_model", dict(N=97, **BIG), EUNSUPPORTED, N97),
+    ("wc_graph_null_model", dict(bin_swaps=-1, period=65), EINVAL, "bin_swaps = -1 < 0"),
+    ("wc_graph_null_model", dict(period=-1, neg_mode=2), EINVAL, "period = -1 < 0"),
+    ("wc_graph_null_model", dict(period=65, neg_mode=2), EUNSUPPORTED, "period = 65 > 64 (the picks of one period, in LDS)"),
+    ("wc_graph_null_model", dict(neg_mode=2, w0=None), EINVAL, "neg_mode = 2, must be 0 (the reference's) or 1 (BCT)"),
+    ("wc_graph_null_model", dict(w0=None, ws_bytes=0), EINVAL, "w, seeds, w0 or workspace is NULL"),
+    ("wc_graph_null_model", dict(ws_bytes=32039, r=P(3) + 4), EINVAL,
+     "ws_bytes = 32039 is less than one slot of 4 N (N - 1) = 32040 bytes"),
+    ("wc_surrogate_fc", dict(B=0, N=1), EINVAL, "B < 1"),
+    ("wc_surrogate_fc", dict(N=1, S=1), EINVAL, "N < 2"),
+    ("wc_surrogate_fc", dict(N=97, S=1), EUNSUPPORTED,
+     "N = 97 > 96 (the products of one matrix per workgroup, in registers)"),
+    ("wc_surrogate_fc", dict(S=1, L=2), EINVAL, "S = 1, needs at least 2 surrogates"),
+    ("wc_surrogate_fc", dict(B=1 << 16, S=1 << 15, L=2), EINVAL, "2^31 surrogates or more (B times S)"),
+    ("wc_surrogate_fc", dict(L=2, spec=None), EINVAL, "L = 2 < 4"),
+    ("wc_surrogate_fc", dict(L=299, spec=None), EINVAL,
+     "L = 299 is odd (the reference's stacked phases need an even length)"),
+    ("wc_surrogate_fc", dict(L=4098, spec=None), EUNSUPPORTED, "L = 4098 > 4096 (wc_spectrogram's longest segment)"),
+    ("wc_surrogate_fc", dict(sfc=None, seeds=P(1) + 4), EINVAL, "spec, seeds or sfc is NULL"),
+    ("wc_surrogate_test", dict(S=1, alpha=0.0), EINVAL, "S = 1, needs at least 2 surrogates"),
+    ("wc_surrogate_test", dict(B=1 << 16, S=1 << 15, alpha=0.0), EINVAL, "2^31 surrogates or more (B times S)"),
+    ("wc_surrogate_test", dict(alpha=1.0, fc=None), EINVAL, "alpha = 1, must lie in (0, 1)"),
+    ("wc_surrogate_test", dict(fc=None, mu=P(4) + 4), EINVAL, "fc, sfc, p_adj or fc_adj is NULL"),
+]
+
+
+@pytest.mark.parametrize("fn, over, code, message", FIRST, ids=[f"{r[0]}-{k}" for k, r in enumerate(FIRST)])
+def test_first_refusal_and_its_message(fn, over, code, message):
+    from nremmodfc_amd import _lib
+    L = _lib.lib()
+    e = next(e for e in ENTRIES if e.fn == fn)
+    assert call(L, e, over) == code
+    assert L.wc_last_error().decode() == f"{fn}: {message}"

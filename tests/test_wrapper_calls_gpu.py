@@ -1,5 +1,7 @@
-"""The library calls behind every public wrapper of sigchain, utils and graph_utils, as literals recorded
-from the commit before their argument handling moved into nremmodfc_amd/_args.py.
+"""The library calls behind every public wrapper of sigchain, utils, graph_utils, partition, nullmodel
+and surrogate (with their numpy facades), as literals recorded from the commit before their argument
+handling moved into nremmodfc_amd/_args.py: the first three before _args.py existed, the seeded three
+before its seeded-run helpers did.
 
 A fixture puts a proxy in the place of _lib.lib(): it forwards every call to libwcsde.so and records the
 entry's name with every scalar argument, "p" or None for every pointer (never its value), the field
@@ -16,7 +18,8 @@ import numpy as np
 import pytest
 import torch
 
-from nremmodfc_amd import _lib, graph_utils as gu, sigchain as sc, utils as ut
+from nremmodfc_amd import (_lib, graph_utils as gu, nullmodel as nm, nullmodel_np as nmn, partition as pt,
+                          partition_np as ptn, sigchain as sc, surrogate as sg, surrogate_np as sgn, utils as ut)
 
 pytestmark = pytest.mark.gpu
 
@@ -123,6 +126,26 @@ def _phase_conn_aec97(d):
 
 
 CI3 = np.array([[0, 1, 0, 1, 1], [1, 1, 0, 0, 1], [0, 0, 0, 1, 1]])
+U64 = [0, 2 ** 64 - 1]                               # the second seed is negative in the int64 view that is uploaded
+CI6 = [0, 0, 0, 1, 1, 1]
+
+
+def signed(dev, seed, *shape):
+    """Exactly symmetric weights of both signs with a zero diagonal, [N][N] or [B][N][N]."""
+    x = rand(dev, seed, *shape)
+    x = (x + x.transpose(-1, -2)) / 2
+    x.diagonal(dim1=-2, dim2=-1).zero_()
+    return x.contiguous()
+
+
+def nsigned(seed, *shape):
+    return signed("cpu", seed, *shape).numpy()
+
+
+def cliques(dev, B=None):
+    """The agreement of two 3-cliques, N = 6: every run finds them, a consensus in one iteration."""
+    D = torch.block_diag(torch.ones(3, 3), torch.ones(3, 3)).double().fill_diagonal_(0).to(dev)
+    return D if B is None else D.expand(B, 6, 6).contiguous()
 
 CASES = {
     "hilbert_phase_8192": lambda d: sc.hilbert_phase(rand(d, 1, 8192, 2)),
@@ -222,6 +245,33 @@ CASES = {
     "welch_peak": lambda d: sc.welch_peak(rand(d, 43, 8000, 1, 1), want_psd=True),
     "bold_stream": _bold_stream,
     "welch_accumulator": _welch_accumulator,
+    # ---- partition, nullmodel, surrogate ----
+    "louvain_sign_seeds_u64_info": lambda d: pt.graph_louvain_sign(signed(d, 60, 2, 6, 6), seeds=U64, want_info=True),
+    "louvain_sign_seed_int_2d": lambda d: pt.graph_louvain_sign(signed(d, 60, 6, 6), seeds=3, gamma=0.9, qtype="neg"),
+    "louvain_sign_one_slot": lambda d: pt.graph_louvain_sign(signed(d, 60, 2, 6, 6), seeds=[1, 2], qtype="smp",
+                                                             ws_bytes=pt.louvain_sign_slot_bytes(6)),
+    "graph_consensus": lambda d: pt.graph_consensus(cliques(d), 0.5, reps=2, max_iter=2),
+    "graph_consensus_batch_seeds": lambda d: pt.graph_consensus(
+        torch.stack([cliques(d), weights(d, 61, 6, 6).clamp(max=1.0)]), 0.3, reps=2, seeds=[2 ** 64 - 1, 5], max_iter=2),
+    "graph_rewire_N4": lambda d: nm.graph_rewire(signed(d, 62, 4, 4)),
+    "graph_rewire_N5_info_one_slot": lambda d: nm.graph_rewire(signed(d, 62, 2, 5, 5), bin_swaps=3, seeds=U64, want_info=True,
+                                                               ws_bytes=nm.null_model_slot_bytes(5)),
+    "graph_null_model_N4": lambda d: nm.graph_null_model(signed(d, 63, 4, 4)),
+    "graph_null_model_N5_stats_one_slot": lambda d: nm.graph_null_model(
+        signed(d, 63, 2, 5, 5), seeds=U64, bin_swaps=2, wei_freq=0.5, negative="reference", want_stats=True,
+        ws_bytes=nm.null_model_slot_bytes(5)),
+    "graph_null_model_sorted_once": lambda d: nm.graph_null_model(signed(d, 63, 5, 5), seeds=[4], wei_freq=0,
+                                                                  want_stats=True),
+    "participation_norm_chunks": lambda d: nm.participation_norm(signed(d, 64, 2, 6, 6), CI6, reps=3,
+                                                                 max_bytes=8 * 2 * 6 * 6),
+    "participation_norm_2d_seeds": lambda d: nm.participation_norm(
+        signed(d, 64, 6, 6), torch.tensor(CI6, device=d), reps=2, seeds=[5, 6], bin_swaps=1, wei_freq=1, negative="reference"),
+    "surrogate_fc": lambda d: sg.surrogate_fc(rand(d, 65, 4, 2), [1, 2]),
+    "surrogate_fc_3d_u64": lambda d: sg.surrogate_fc(rand(d, 65, 4, 2, 2), U64),
+    "fc_surrogate_test_chunks": lambda d: sg.fc_surrogate_test(rand(d, 66, 8, 3, 3), surr_number=2,
+                                                               ws_bytes=sg.surrogate_slab_bytes(3, 2)),
+    "fc_surrogate_test_2d_stats": lambda d: sg.fc_surrogate_test(rand(d, 66, 8, 3), surr_number=2, alpha=0.1, seeds=[3, 4],
+                                                                 want_stats=True),
     # ---- utils ----
     "utils_envelope": lambda d: ut.envelope(nrand(44, 60), fcut=2.0),
     "utils_welch": lambda d: ut.welch(nrand(45, 3, 64), nperseg=8, nfft=8),
@@ -257,6 +307,16 @@ CASES = {
     "graph_utils_agreement": lambda d: gu.agreement(np.array([[1, 1, 2], [1, 2, 2], [3, 2, 2], [3, 3, 1]])),
     "graph_utils_get_agreement_matrix": lambda d: (gu.get_agreement_matrix(nweights(57, 5, 5), reps=2),
                                                    gu.get_agreement_matrix(nweights(57, 5, 5), reps=2, seeds=[4, 5])),
+    "graph_utils_louvain_sign": lambda d: (ptn.modularity_louvain_und_sign(nsigned(67, 6, 6), seed=1),
+                                           ptn.modularity_louvain_und_sign(nsigned(67, 2, 6, 6), gamma=0.8, qtype="gja",
+                                                                           seed=2 ** 64 - 1)),
+    "graph_utils_consensus_und": lambda d: (ptn.consensus_und(cliques("cpu").numpy(), 0.5, reps=2),
+                                            ptn.consensus_und(cliques("cpu", 2).numpy(), 0.5, reps=3)),
+    "graph_utils_null_models": lambda d: (nmn.randmio_und_signed(nsigned(69, 5, 5), 2, seed=1),
+                                          nmn.null_model_und_sign(nsigned(69, 5, 5), bin_swaps=2, wei_freq=0.5, seed=2),
+                                          nmn.participation_coef_norm(nsigned(69, 6, 6), CI6, BA_iters=2)),
+    "graph_utils_probabilistic_thresholding": lambda d: (sgn.probabilistic_thresholding(nrand(68, 8, 3), surr_number=2),
+                                                         sgn.probabilistic_thresholding(nrand(68, 2, 8, 3), 3, alpha=0.2)),
     "graph_utils_host_helpers": lambda d: (gu.get_uptri(nrand(59, 4, 4)), gu.matrix_recon(nrand(59, 6)),
                                            gu.thresholding(nweights(59, 6, 6), 0.5),
                                            gu.thresholding(nweights(59, 6, 6), 0.5, direct="directed"),
@@ -690,4 +750,75 @@ PLAN = {'hilbert_phase_8192': [('wc_hilbert_phase', 2, 8192, 'p', 'p', 'p', 6553
                                       ('wc_graph_agreement', 1, 2, 5, 'p', 'p', 'p'),
                                       ('wc_graph_louvain', 1, 2, 5, 'p', 'p', None, 'p', 'p', 'p', None, 'p'),
                                       ('wc_graph_agreement', 1, 2, 5, 'p', 'p', 'p')],
- 'graph_utils_host_helpers': []}
+ 'graph_utils_host_helpers': [],
+ # recorded at the commit before the seeded wrappers moved onto _args.py's seeded-run helpers, on an MI355X
+ 'louvain_sign_seeds_u64_info': [('wc_graph_louvain_sign', 2, 2, 6, 'p', 1.0, 0, 'p', 'p', 'p', 'p', 'p', 2304, 'p')],
+ 'louvain_sign_seed_int_2d': [('wc_graph_louvain_sign', 1, 1, 6, 'p', 0.9, 4, 'p', 'p', 'p', None, 'p', 576, 'p')],
+ 'louvain_sign_one_slot': [('wc_graph_louvain_sign', 2, 2, 6, 'p', 1.0, 2, 'p', 'p', 'p', None, 'p', 576, 'p')],
+ 'graph_consensus': [('wc_graph_louvain_sign', 1, 2, 6, 'p', 1.0, 0, 'p', 'p', 'p', None, 'p', 1152, 'p'),
+                     ('wc_graph_agreement', 1, 2, 6, 'p', 'p', 'p')],
+ 'graph_consensus_batch_seeds': [('wc_graph_louvain_sign', 2, 2, 6, 'p', 1.0, 0, 'p', 'p', 'p', None, 'p', 2304, 'p'),
+                                 ('wc_graph_agreement', 2, 2, 6, 'p', 'p', 'p')],
+ 'graph_rewire_N4': [('wc_graph_rewire', 1, 1, 4, 'p', 5, 'p', 'p', None, 'p', 48, 'p')],
+ 'graph_rewire_N5_info_one_slot': [('wc_graph_rewire', 2, 2, 5, 'p', 3, 'p', 'p', 'p', 'p', 80, 'p')],
+ 'graph_null_model_N4': [('wc_graph_null_model', 1, 1, 4, 'p', 5, 10, 1, 'p', 'p', None, None, 'p', 48, 'p')],
+ 'graph_null_model_N5_stats_one_slot': [('wc_graph_null_model', 2, 2, 5, 'p', 2, 2, 0, 'p', 'p', 'p', 'p', 'p', 80,
+                                         'p')],
+ 'graph_null_model_sorted_once': [('wc_graph_null_model', 1, 1, 5, 'p', 5, 0, 1, 'p', 'p', 'p', 'p', 'p', 80, 'p')],
+ 'participation_norm_chunks': [('wc_graph_null_model', 2, 1, 6, 'p', 5, 10, 1, 'p', 'p', 'p', 'p', 'p', 240, 'p'),
+                               ('wc_graph_null_model', 2, 1, 6, 'p', 5, 10, 1, 'p', 'p', 'p', 'p', 'p', 240, 'p'),
+                               ('wc_graph_null_model', 2, 1, 6, 'p', 5, 10, 1, 'p', 'p', 'p', 'p', 'p', 240, 'p')],
+ 'participation_norm_2d_seeds': [('wc_graph_null_model', 1, 2, 6, 'p', 1, 1, 0, 'p', 'p', 'p', 'p', 'p', 240, 'p')],
+ 'surrogate_fc': [('wc_spectrogram_workspace_size', 4),
+                  ('wc_spectrogram', 2, 4, 'p', 4, 0, 'p', 1, 1.0, 1, 'p', 'p', 132352, 'p'),
+                  ('wc_surrogate_fc', 1, 2, 4, 2, 'p', 'p', 'p', 'p')],
+ 'surrogate_fc_3d_u64': [('wc_spectrogram_workspace_size', 4),
+                         ('wc_spectrogram', 4, 4, 'p', 4, 0, 'p', 1, 1.0, 1, 'p', 'p', 132352, 'p'),
+                         ('wc_surrogate_fc', 2, 2, 4, 2, 'p', 'p', 'p', 'p')],
+ 'fc_surrogate_test_chunks': [('wc_spectrogram_workspace_size', 8),
+                              ('wc_spectrogram', 3, 8, 'p', 8, 0, 'p', 1, 1.0, 1, 'p', 'p', 132352, 'p'),
+                              ('wc_surrogate_fc', 1, 3, 8, 2, 'p', 'p', 'p', 'p'),
+                              ('wc_corrcoef_workspace_size', 1, 3, 8),
+                              ('wc_corrcoef', 1, 3, 8, 'p', 'p', 'p', 128, 'p'),
+                              ('wc_surrogate_test', 1, 3, 2, 'p', 'p', 0.05, 'p', 'p', None, None, None, 'p'),
+                              ('wc_spectrogram_workspace_size', 8),
+                              ('wc_spectrogram', 3, 8, 'p', 8, 0, 'p', 1, 1.0, 1, 'p', 'p', 132352, 'p'),
+                              ('wc_surrogate_fc', 1, 3, 8, 2, 'p', 'p', 'p', 'p'),
+                              ('wc_corrcoef_workspace_size', 1, 3, 8),
+                              ('wc_corrcoef', 1, 3, 8, 'p', 'p', 'p', 128, 'p'),
+                              ('wc_surrogate_test', 1, 3, 2, 'p', 'p', 0.05, 'p', 'p', None, None, None, 'p'),
+                              ('wc_spectrogram_workspace_size', 8),
+                              ('wc_spectrogram', 3, 8, 'p', 8, 0, 'p', 1, 1.0, 1, 'p', 'p', 132352, 'p'),
+                              ('wc_surrogate_fc', 1, 3, 8, 2, 'p', 'p', 'p', 'p'),
+                              ('wc_corrcoef_workspace_size', 1, 3, 8),
+                              ('wc_corrcoef', 1, 3, 8, 'p', 'p', 'p', 128, 'p'),
+                              ('wc_surrogate_test', 1, 3, 2, 'p', 'p', 0.05, 'p', 'p', None, None, None, 'p')],
+ 'fc_surrogate_test_2d_stats': [('wc_spectrogram_workspace_size', 8),
+                                ('wc_spectrogram', 3, 8, 'p', 8, 0, 'p', 1, 1.0, 1, 'p', 'p', 132352, 'p'),
+                                ('wc_surrogate_fc', 1, 3, 8, 2, 'p', 'p', 'p', 'p'),
+                                ('wc_corrcoef_workspace_size', 1, 3, 8),
+                                ('wc_corrcoef', 1, 3, 8, 'p', 'p', 'p', 128, 'p'),
+                                ('wc_surrogate_test', 1, 3, 2, 'p', 'p', 0.1, 'p', 'p', 'p', 'p', 'p', 'p')],
+ 'graph_utils_louvain_sign': [('wc_graph_louvain_sign', 1, 1, 6, 'p', 1.0, 0, 'p', 'p', 'p', None, 'p', 576, 'p'),
+                              ('wc_graph_louvain_sign', 2, 1, 6, 'p', 0.8, 3, 'p', 'p', 'p', None, 'p', 1152, 'p')],
+ 'graph_utils_consensus_und': [('wc_graph_louvain_sign', 1, 2, 6, 'p', 1.0, 0, 'p', 'p', 'p', None, 'p', 1152, 'p'),
+                               ('wc_graph_agreement', 1, 2, 6, 'p', 'p', 'p'),
+                               ('wc_graph_louvain_sign', 2, 3, 6, 'p', 1.0, 0, 'p', 'p', 'p', None, 'p', 3456, 'p'),
+                               ('wc_graph_agreement', 2, 3, 6, 'p', 'p', 'p')],
+ 'graph_utils_null_models': [('wc_graph_rewire', 1, 1, 5, 'p', 2, 'p', 'p', 'p', 'p', 80, 'p'),
+                             ('wc_graph_null_model', 1, 1, 5, 'p', 2, 2, 0, 'p', 'p', 'p', 'p', 'p', 80, 'p'),
+                             ('wc_graph_null_model', 1, 2, 6, 'p', 5, 10, 0, 'p', 'p', 'p', 'p', 'p', 240, 'p')],
+ 'graph_utils_probabilistic_thresholding': [('wc_spectrogram_workspace_size', 8),
+                                            ('wc_spectrogram', 3, 8, 'p', 8, 0, 'p', 1, 1.0, 1, 'p', 'p', 132352, 'p'),
+                                            ('wc_surrogate_fc', 1, 3, 8, 2, 'p', 'p', 'p', 'p'),
+                                            ('wc_corrcoef_workspace_size', 1, 3, 8),
+                                            ('wc_corrcoef', 1, 3, 8, 'p', 'p', 'p', 128, 'p'),
+                                            ('wc_surrogate_test', 1, 3, 2, 'p', 'p', 0.05, 'p', 'p', None, None, None,
+                                             'p'),
+                                            ('wc_spectrogram_workspace_size', 8),
+                                            ('wc_spectrogram', 6, 8, 'p', 8, 0, 'p', 1, 1.0, 1, 'p', 'p', 132352, 'p'),
+                                            ('wc_surrogate_fc', 2, 3, 8, 3, 'p', 'p', 'p', 'p'),
+                                            ('wc_corrcoef_workspace_size', 2, 3, 8),
+                                            ('wc_corrcoef', 2, 3, 8, 'p', 'p', 'p', 248, 'p'),
+                                            ('wc_surrogate_test', 2, 3, 3, 'p', 'p', 0.2, 'p', 'p', None, None, None,
+                                             'p')]}

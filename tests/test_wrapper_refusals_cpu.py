@@ -1,6 +1,8 @@
-"""What the Python wrappers (sigchain, utils, graph_utils) refuse, and their public surface, as literals
-recorded from the commit before their argument handling moved into nremmodfc_amd/_args.py (no GPU:
-every row is refused before the device is touched, so CPU tensors and numpy arrays are enough).
+"""What the Python wrappers (sigchain, utils, graph_utils; partition, nullmodel, surrogate and their numpy
+facades) refuse, and their public surface, as literals recorded from the commit before their argument
+handling moved into nremmodfc_amd/_args.py: the first three modules before _args.py existed, the other
+six before its number gates and seeded-run helpers did (no GPU: every row is refused before the device
+is touched, so CPU tensors and numpy arrays are enough).
 
 ROWS: one row per `raise` statement of the three modules, as (id, call, exception class, exact
 message), plus rows that show a shared helper under each wrapper's name.  At the recorded commit the
@@ -10,6 +12,14 @@ and BoldStream.finish are called on a plain namespace, since a real BoldStream i
 the device; graph_module_measures' "same device" refusal takes a ci on torch's meta device; and
 utils.kuramoto uploads before it looks at the shape, so its row runs with utils.device = "cpu".
 
+The seeded modules, at their recorded commit: partition 7 `raise` statements, nullmodel 11, surrogate 7,
+all with a row, most with one per way of failing the test (a bool, a float, a bound), and the shared
+helpers (seeds, the matrix stack, the series) under each wrapper's name.  nullmodel_np has 11: 7 have
+rows, the 3 of _refused, which reads a status the device wrote, are called directly, and "a null model
+was refused" comes after device work and has none.  partition_np's 2 (consensus_und's non-finite D and
+its missing consensus) both come after device work and have none; its rows show graph_utils._matrices
+under its names.  surrogate_np's 2 have rows, and surrogate._test_args shows under its name.
+
 PTR_ROWS: calls in which a CPU tensor passes every check of the wrapper and _lib.ptr refuses it.  A
 wrapper that asks for the stream first (graph_measures) shows torch's own error instead, which is not a
 refusal of this package and has no row.
@@ -17,7 +27,8 @@ refusal of this package and has no row.
 DOUBLE_ROWS: calls that are wrong in two ways, which pin the order of the checks.  The SciPy facades
 disagree among themselves (utils.welch and utils.spectrogram look at nfft before complex input,
 utils.csd and utils.coherence the other way round); each keeps its own order.  utils.coherence has no
-return_onesided parameter, so its second row is Python's own TypeError.
+return_onesided parameter, so its second row is Python's own TypeError.  Every public wrapper of
+partition, nullmodel and surrogate has a chain of rows, each wrong in its k-th and (k+1)-th check.
 
 Then the clamped-nperseg UserWarning of welch, csd, coherence and spectrogram, which must name the
 caller's file, and inspect.signature of every public callable and the value of every public constant.
@@ -30,7 +41,8 @@ import numpy as np
 import pytest
 import torch
 
-from nremmodfc_amd import _lib, graph_utils as gu, sigchain as sc, utils as ut
+from nremmodfc_amd import (_lib, graph_utils as gu, nullmodel as nm, nullmodel_np as nmn, partition as pt,
+                          partition_np as ptn, sigchain as sc, surrogate as sg, surrogate_np as sgn, utils as ut)
 
 WCSDEError = _lib.WCSDEError
 
@@ -73,6 +85,11 @@ CM = "['plv', 'pli', 'wpli', 'aec', 'aec_orth']"
 STACK = "w must be a [B][N][N] or [N][N] fp64 device tensor"
 STACK_N = "needs B >= 1 and 2 <= N <= 96 (one matrix per workgroup, in LDS)"
 X64, Z64, ONES3 = np.zeros(64), np.zeros(64, dtype=complex), np.ones((3, 3))
+QT = "['sta', 'pos', 'smp', 'gja', 'neg']"
+SEEDS = "seeds must be an int or a non-empty sequence of ints in [0, 2^64), got "
+SERIES = "x must be a [L][N] or time-major [L][B][N] fp64 device tensor"
+EVEN_L = "needs an even number of samples, at least 4 (the reference's stacked phases need an even length)"
+LAB4 = [0, 0, 1, 1]
 
 ROWS = [
     # ---- sigchain ----
@@ -427,6 +444,194 @@ ROWS = [
      "agreement: N = 1, the device kernels take 2 <= N <= 96"),
     ("g_consensus_seeds", lambda: gu.get_agreement_matrix(ONES3, reps=2, seeds=[1]), ValueError,
      "get_agreement_matrix: seeds must be an array of length equal to reps, or None"),
+    # ---- partition ----
+    ("pt_sign_qtype", lambda: pt.graph_louvain_sign(f64(3, 3), qtype="nope"), ValueError,
+     "graph_louvain_sign: modularity type unknown: qtype 'nope', must be one of " + QT),
+    ("pt_sign_qtype_int", lambda: pt.graph_louvain_sign(f64(3, 3), qtype=0), ValueError,
+     "graph_louvain_sign: modularity type unknown: qtype 0, must be one of " + QT),
+    ("pt_sign_gamma_inf", lambda: pt.graph_louvain_sign(f64(3, 3), gamma=float("inf")), ValueError,
+     "graph_louvain_sign: gamma = inf, must be a finite number"),
+    ("pt_sign_gamma_bool", lambda: pt.graph_louvain_sign(f64(3, 3), gamma=True), ValueError,
+     "graph_louvain_sign: gamma = True, must be a finite number"),
+    ("pt_sign_gamma_str", lambda: pt.graph_louvain_sign(f64(3, 3), gamma="1"), ValueError,
+     "graph_louvain_sign: gamma = '1', must be a finite number"),
+    ("pt_sign_seeds", lambda: pt.graph_louvain_sign(f64(3, 3), seeds=-1), ValueError, "graph_louvain_sign: " + SEEDS + "-1"),
+    ("pt_sign_seeds_empty", lambda: pt.graph_louvain_sign(f64(3, 3), seeds=[]), ValueError,
+     "graph_louvain_sign: " + SEEDS + "[]"),
+    ("pt_sign_seeds_bool", lambda: pt.graph_louvain_sign(f64(3, 3), seeds=[0, True]), ValueError,
+     "graph_louvain_sign: " + SEEDS + "[0, True]"),
+    ("pt_sign_seeds_2_64", lambda: pt.graph_louvain_sign(f64(3, 3), seeds=[1 << 64]), ValueError,
+     "graph_louvain_sign: " + SEEDS + "[18446744073709551616]"),
+    ("pt_sign_seeds_set", lambda: pt.graph_louvain_sign(f64(3, 3), seeds={1}), ValueError,
+     "graph_louvain_sign: " + SEEDS + "{1}"),
+    ("pt_sign_w", lambda: pt.graph_louvain_sign(f32(3, 3)), TypeError, "graph_louvain_sign: " + STACK),
+    ("pt_sign_N97", lambda: pt.graph_louvain_sign(f64(2, 97, 97)), ValueError,
+     "graph_louvain_sign: N = 97, B = 2: " + STACK_N),
+    ("pt_sign_ws", lambda: pt.graph_louvain_sign(f64(3, 3), ws_bytes=143), ValueError,
+     "graph_louvain_sign: ws_bytes = 143, needs at least one slot of 16 N^2 = 144 bytes"),
+    ("pt_sign_ws_bool", lambda: pt.graph_louvain_sign(f64(3, 3), ws_bytes=True), ValueError,
+     "graph_louvain_sign: ws_bytes = True, needs at least one slot of 16 N^2 = 144 bytes"),
+    ("pt_sign_ws_float", lambda: pt.graph_louvain_sign(f64(3, 3), ws_bytes=144.0), ValueError,
+     "graph_louvain_sign: ws_bytes = 144.0, needs at least one slot of 16 N^2 = 144 bytes"),
+    ("pt_consensus_reps", lambda: pt.graph_consensus(f64(3, 3), 0.5, reps=0), ValueError,
+     "graph_consensus: reps = 0, must be a positive int"),
+    ("pt_consensus_reps_float", lambda: pt.graph_consensus(f64(3, 3), 0.5, reps=2.0), ValueError,
+     "graph_consensus: reps = 2.0, must be a positive int"),
+    ("pt_consensus_max_iter", lambda: pt.graph_consensus(f64(3, 3), 0.5, reps=2, max_iter=0), ValueError,
+     "graph_consensus: max_iter = 0, must be a positive int"),
+    ("pt_consensus_max_iter_bool", lambda: pt.graph_consensus(f64(3, 3), 0.5, reps=2, max_iter=True), ValueError,
+     "graph_consensus: max_iter = True, must be a positive int"),
+    ("pt_consensus_tau", lambda: pt.graph_consensus(f64(3, 3), float("nan"), reps=2), ValueError,
+     "graph_consensus: tau = nan, must be a finite number"),
+    ("pt_consensus_tau_none", lambda: pt.graph_consensus(f64(3, 3), None, reps=2), ValueError,
+     "graph_consensus: tau = None, must be a finite number"),
+    ("pt_consensus_seeds_len", lambda: pt.graph_consensus(f64(3, 3), 0.5, reps=2, seeds=[1]), ValueError,
+     "graph_consensus: seeds must be a sequence of length reps = 2, or None"),
+    ("pt_consensus_seeds_int", lambda: pt.graph_consensus(f64(3, 3), 0.5, reps=2, seeds=3), ValueError,
+     "graph_consensus: seeds must be a sequence of length reps = 2, or None"),
+    ("pt_consensus_seeds_value", lambda: pt.graph_consensus(f64(3, 3), 0.5, reps=2, seeds=[-1, 0]), ValueError,
+     "graph_consensus: " + SEEDS + "[-1, 0]"),
+    ("pt_consensus_D", lambda: pt.graph_consensus(f32(3, 3), 0.5, reps=2), TypeError, "graph_consensus: " + STACK),
+    # ---- nullmodel ----
+    ("nm_rewire_N", lambda: nm.graph_rewire(f64(3, 3)), ValueError,
+     "graph_rewire: N = 3, a rewiring takes four distinct nodes: needs N >= 4"),
+    ("nm_rewire_w", lambda: nm.graph_rewire(f32(4, 4)), TypeError, "graph_rewire: " + STACK),
+    ("nm_rewire_N97", lambda: nm.graph_rewire(f64(97, 97)), ValueError, "graph_rewire: N = 97, B = 1: " + STACK_N),
+    ("nm_rewire_seeds", lambda: nm.graph_rewire(f64(4, 4), seeds=1.0), ValueError, "graph_rewire: " + SEEDS + "1.0"),
+    ("nm_rewire_swaps", lambda: nm.graph_rewire(f64(4, 4), bin_swaps=-1), ValueError,
+     "graph_rewire: bin_swaps = -1, must be an int >= 0"),
+    ("nm_rewire_swaps_bool", lambda: nm.graph_rewire(f64(4, 4), bin_swaps=True), ValueError,
+     "graph_rewire: bin_swaps = True, must be an int >= 0"),
+    ("nm_rewire_swaps_float", lambda: nm.graph_rewire(f64(4, 4), bin_swaps=1.0), ValueError,
+     "graph_rewire: bin_swaps = 1.0, must be an int >= 0"),
+    ("nm_rewire_swaps_2_31", lambda: nm.graph_rewire(f64(4, 4), bin_swaps=119304648), ValueError,
+     "graph_rewire: bin_swaps = 119304648: its iterations times 3 attempts reach 2^31"),
+    ("nm_rewire_swaps_2_31_odd", lambda: nm.graph_rewire(f64(5, 5), bin_swaps=71582789), ValueError,
+     "graph_rewire: bin_swaps = 71582789: its iterations times 3 attempts reach 2^31"),
+    ("nm_rewire_ws", lambda: nm.graph_rewire(f64(4, 4), ws_bytes=47), ValueError,
+     "graph_rewire: ws_bytes = 47, needs at least one slot of 4 N (N - 1) = 48 bytes"),
+    ("nm_rewire_ws_bool", lambda: nm.graph_rewire(f64(4, 4), ws_bytes=True), ValueError,
+     "graph_rewire: ws_bytes = True, needs at least one slot of 4 N (N - 1) = 48 bytes"),
+    ("nm_null_negative", lambda: nm.graph_null_model(f64(4, 4), negative="nope"), ValueError,
+     "graph_null_model: negative = 'nope', must be one of ['reference', 'bct']"),
+    ("nm_null_wei_freq", lambda: nm.graph_null_model(f64(4, 4), wei_freq=2), ValueError,
+     "graph_null_model: wei_freq = 2, must be a number in [0, 1]"),
+    ("nm_null_wei_freq_bool", lambda: nm.graph_null_model(f64(4, 4), wei_freq=True), ValueError,
+     "graph_null_model: wei_freq = True, must be a number in [0, 1]"),
+    ("nm_null_wei_freq_nan", lambda: nm.graph_null_model(f64(4, 4), wei_freq=float("nan")), ValueError,
+     "graph_null_model: wei_freq = nan, must be a number in [0, 1]"),
+    ("nm_null_period", lambda: nm.graph_null_model(f64(4, 4), wei_freq=0.01), ValueError,
+     "graph_null_model: wei_freq = 0.01 is a period of 100 > 64; 0 sorts once"),
+    ("nm_null_seeds", lambda: nm.graph_null_model(f64(4, 4), seeds="1"), ValueError, "graph_null_model: " + SEEDS + "'1'"),
+    ("nm_null_N", lambda: nm.graph_null_model(f64(2, 3, 3)), ValueError,
+     "graph_null_model: N = 3, a rewiring takes four distinct nodes: needs N >= 4"),
+    ("nm_null_swaps", lambda: nm.graph_null_model(f64(4, 4), bin_swaps=-1), ValueError,
+     "graph_null_model: bin_swaps = -1, must be an int >= 0"),
+    ("nm_null_ws", lambda: nm.graph_null_model(f64(5, 5), ws_bytes=79), ValueError,
+     "graph_null_model: ws_bytes = 79, needs at least one slot of 4 N (N - 1) = 80 bytes"),
+    ("nm_pnorm_reps", lambda: nm.participation_norm(f64(4, 4), LAB4, reps=0), ValueError,
+     "participation_norm: reps = 0, must be a positive int"),
+    ("nm_pnorm_reps_bool", lambda: nm.participation_norm(f64(4, 4), LAB4, reps=True), ValueError,
+     "participation_norm: reps = True, must be a positive int"),
+    ("nm_pnorm_max_bytes", lambda: nm.participation_norm(f64(4, 4), LAB4, reps=2, max_bytes=0), ValueError,
+     "participation_norm: max_bytes = 0, must be a positive int"),
+    ("nm_pnorm_max_bytes_float", lambda: nm.participation_norm(f64(4, 4), LAB4, reps=2, max_bytes=1e6), ValueError,
+     "participation_norm: max_bytes = 1000000.0, must be a positive int"),
+    ("nm_pnorm_seeds_len", lambda: nm.participation_norm(f64(4, 4), LAB4, reps=2, seeds=[1]), ValueError,
+     "participation_norm: seeds must be a sequence of length reps = 2, or None"),
+    ("nm_pnorm_seeds_int", lambda: nm.participation_norm(f64(4, 4), LAB4, reps=2, seeds=7), ValueError,
+     "participation_norm: seeds must be a sequence of length reps = 2, or None"),
+    ("nm_pnorm_seeds_value", lambda: nm.participation_norm(f64(4, 4), LAB4, reps=2, seeds=[0, -1]), ValueError,
+     "participation_norm: " + SEEDS + "[0, -1]"),
+    ("nm_pnorm_negative", lambda: nm.participation_norm(f64(4, 4), LAB4, reps=2, negative=1), ValueError,
+     "participation_norm: negative = 1, must be one of ['reference', 'bct']"),
+    ("nm_pnorm_wei_freq", lambda: nm.participation_norm(f64(4, 4), LAB4, reps=2, wei_freq=-0.1), ValueError,
+     "participation_norm: wei_freq = -0.1, must be a number in [0, 1]"),
+    ("nm_pnorm_N", lambda: nm.participation_norm(f64(3, 3), [0, 0, 1], reps=2), ValueError,
+     "participation_norm: N = 3, a rewiring takes four distinct nodes: needs N >= 4"),
+    ("nm_pnorm_swaps", lambda: nm.participation_norm(f64(4, 4), LAB4, reps=2, bin_swaps=None), ValueError,
+     "participation_norm: bin_swaps = None, must be an int >= 0"),
+    ("nm_pnorm_labels", lambda: nm.participation_norm(f64(4, 4), [0, 0, 1], reps=2), TypeError,
+     "participation_norm: ci must hold integer labels, [N] or [B][N] with N = 4, B = 1"),
+    # ---- surrogate ----
+    ("sg_fc_x", lambda: sg.surrogate_fc(f32(4, 2), [1, 2]), TypeError, "surrogate_fc: " + SERIES),
+    ("sg_fc_L_odd", lambda: sg.surrogate_fc(f64(5, 2), [1, 2]), ValueError, "surrogate_fc: L = 5, " + EVEN_L),
+    ("sg_fc_L_2", lambda: sg.surrogate_fc(f64(2, 2), [1, 2]), ValueError, "surrogate_fc: L = 2, " + EVEN_L),
+    ("sg_fc_L_max", lambda: sg.surrogate_fc(f64(4098, 2), [1, 2]), ValueError,
+     "surrogate_fc: L = 4098 > 4096 (one transform per workgroup, in LDS)"),
+    ("sg_fc_N", lambda: sg.surrogate_fc(f64(4, 1), [1, 2]), ValueError,
+     "surrogate_fc: N = 1, B = 1: needs B >= 1 and 2 <= N <= 96 (the result feeds the graph kernels)"),
+    ("sg_fc_B", lambda: sg.surrogate_fc(f64(4, 0, 2), [1, 2]), ValueError,
+     "surrogate_fc: N = 2, B = 0: needs B >= 1 and 2 <= N <= 96 (the result feeds the graph kernels)"),
+    ("sg_fc_seeds_one", lambda: sg.surrogate_fc(f64(4, 2), [1]), ValueError,
+     "surrogate_fc: seeds must be a sequence of at least 2 ints in [0, 2^64), got [1]"),
+    ("sg_fc_seeds_int", lambda: sg.surrogate_fc(f64(4, 2), 5), ValueError,
+     "surrogate_fc: seeds must be a sequence of at least 2 ints in [0, 2^64), got 5"),
+    ("sg_fc_seeds_value", lambda: sg.surrogate_fc(f64(4, 2), [1, -2]), ValueError, "surrogate_fc: " + SEEDS + "[1, -2]"),
+    ("sg_test_surr_number", lambda: sg.fc_surrogate_test(f64(4, 2), surr_number=1), ValueError,
+     "fc_surrogate_test: surr_number = 1, must be an int of at least 2"),
+    ("sg_test_surr_number_float", lambda: sg.fc_surrogate_test(f64(4, 2), surr_number=2.0), ValueError,
+     "fc_surrogate_test: surr_number = 2.0, must be an int of at least 2"),
+    ("sg_test_alpha_1", lambda: sg.fc_surrogate_test(f64(4, 2), surr_number=2, alpha=1), ValueError,
+     "fc_surrogate_test: alpha = 1, must lie in (0, 1)"),
+    ("sg_test_alpha_0", lambda: sg.fc_surrogate_test(f64(4, 2), surr_number=2, alpha=0.0), ValueError,
+     "fc_surrogate_test: alpha = 0.0, must lie in (0, 1)"),
+    ("sg_test_alpha_bool", lambda: sg.fc_surrogate_test(f64(4, 2), surr_number=2, alpha=False), ValueError,
+     "fc_surrogate_test: alpha = False, must lie in (0, 1)"),
+    ("sg_test_seeds_len", lambda: sg.fc_surrogate_test(f64(4, 2), surr_number=2, seeds=[1, 2, 3]), ValueError,
+     "fc_surrogate_test: seeds must be a sequence of surr_number = 2 ints in [0, 2^64), got [1, 2, 3]"),
+    ("sg_test_seeds_int", lambda: sg.fc_surrogate_test(f64(4, 2), surr_number=2, seeds=4), ValueError,
+     "fc_surrogate_test: seeds must be a sequence of surr_number = 2 ints in [0, 2^64), got 4"),
+    ("sg_test_seeds_value", lambda: sg.fc_surrogate_test(f64(4, 2), surr_number=2, seeds=[1, 2.0]), ValueError,
+     "fc_surrogate_test: " + SEEDS + "[1, 2.0]"),
+    ("sg_test_L", lambda: sg.fc_surrogate_test(f64(7, 2), surr_number=2), ValueError, "fc_surrogate_test: L = 7, " + EVEN_L),
+    ("sg_test_ws", lambda: sg.fc_surrogate_test(f64(4, 3), surr_number=2, ws_bytes=47), ValueError,
+     "fc_surrogate_test: ws_bytes = 47, needs at least one simulation's slab of 8 S P = 48 bytes"),
+    ("sg_test_ws_bool", lambda: sg.fc_surrogate_test(f64(4, 3), surr_number=2, ws_bytes=True), ValueError,
+     "fc_surrogate_test: ws_bytes = True, needs at least one simulation's slab of 8 S P = 48 bytes"),
+    # ---- partition_np, nullmodel_np, surrogate_np ----
+    ("ptn_sign_shape", lambda: ptn.modularity_louvain_und_sign(np.zeros(3)), ValueError,
+     "modularity_louvain_und_sign: needs an N x N matrix or a [B, N, N] stack, got shape (3,)"),
+    ("ptn_consensus_N", lambda: ptn.consensus_und(np.zeros((1, 1)), 0.5), ValueError,
+     "consensus_und: N = 1, the device kernels take 2 <= N <= 96"),
+    ("nmn_shape", lambda: nmn.randmio_und_signed(np.zeros(3), 1), ValueError,
+     "randmio_und_signed: needs an N x N matrix, got shape (3,)"),
+    ("nmn_N", lambda: nmn.null_model_und_sign(np.zeros((3, 3))), ValueError,
+     "null_model_und_sign: N = 3, the device kernel takes 4 <= N <= 96"),
+    ("nmn_N97", lambda: nmn.participation_coef_norm(np.zeros((97, 97)), np.zeros(97)), ValueError,
+     "participation_coef_norm: N = 97, the device kernel takes 4 <= N <= 96"),
+    ("nmn_itr", lambda: nmn.randmio_und_signed(np.zeros((4, 4)), -1), ValueError,
+     "randmio_und_signed: itr = -1, must be an int >= 0"),
+    ("nmn_itr_bool", lambda: nmn.randmio_und_signed(np.zeros((4, 4)), True), ValueError,
+     "randmio_und_signed: itr = True, must be an int >= 0"),
+    ("nmn_itr_fraction", lambda: nmn.randmio_und_signed(np.zeros((4, 4)), 1.5), ValueError,
+     "randmio_und_signed: itr = 1.5, must be an int >= 0"),
+    ("nmn_null_directed", lambda: nmn.null_model_und_sign(np.triu(np.ones((4, 4)), 1)), TypeError,
+     "Input must be undirected"),
+    ("nmn_pnorm_degree", lambda: nmn.participation_coef_norm(np.zeros((4, 4)), LAB4, degree="both"), ValueError,
+     "participation_coef_norm: degree 'both', must be 'undirected', 'in' or 'out'"),
+    ("nmn_pnorm_directed", lambda: nmn.participation_coef_norm(np.triu(np.ones((4, 4)), 1), LAB4), TypeError,
+     "Input must be undirected"),
+    ("nmn_pnorm_labels", lambda: nmn.participation_coef_norm(np.zeros((4, 4)), [0, 1]), ValueError,
+     "participation_coef_norm: ci needs one label per node, got shape (2,)"),
+    ("nmn_status_3", lambda: nmn._refused("randmio_und_signed", None, 3), ValueError,
+     "randmio_und_signed: the matrix holds NaN or inf"),
+    ("nmn_status_2", lambda: nmn._refused("null_model_und_sign", None, 2), TypeError, "Input must be undirected"),
+    ("nmn_status_1", lambda: nmn._refused("null_model_und_sign", None, 1), ZeroDivisionError,
+     "null_model_und_sign: a strength reached exactly 0 where the reference divides by it"),
+    ("sgn_conn", lambda: sgn.probabilistic_thresholding(np.zeros((4, 2)), conn="plv"), KeyError,
+     "'invalid connectivity metric'"),
+    ("sgn_y", lambda: sgn.probabilistic_thresholding(np.zeros(3)), TypeError,
+     "probabilistic_thresholding: y must be a real [L, N] array or a [B, L, N] stack, got shape (3,), dtype float64"),
+    ("sgn_y_complex", lambda: sgn.probabilistic_thresholding(np.zeros((4, 2), dtype=complex)), TypeError,
+     "probabilistic_thresholding: y must be a real [L, N] array or a [B, L, N] stack, got shape (4, 2), dtype "
+     "complex128"),
+    ("sgn_surr_number", lambda: sgn.probabilistic_thresholding(np.zeros((4, 2)), surr_number=1), ValueError,
+     "probabilistic_thresholding: surr_number = 1, must be an int of at least 2"),
+    ("sgn_alpha", lambda: sgn.probabilistic_thresholding(np.zeros((4, 2)), alpha=2), ValueError,
+     "probabilistic_thresholding: alpha = 2, must lie in (0, 1)"),
+    ("sgn_L", lambda: sgn.probabilistic_thresholding(np.zeros((2, 5, 3))), ValueError,
+     "probabilistic_thresholding: L = 5, " + EVEN_L),
 ]
 ROWS += [("g_shape_" + n, (lambda f: lambda: f(np.zeros(3)))(getattr(gu, n)), ValueError,
           n + ": needs an N x N matrix or a [B, N, N] stack, got shape (3,)")
@@ -475,6 +680,14 @@ PTR_ROWS = [(name, call, WCSDEError, DEVICE_ONLY) for name, call in [
     ("utils_envelope", lambda: on_cpu(ut.envelope, np.zeros((30, 2)))),
     ("utils_welch", lambda: on_cpu(ut.welch, X64, nperseg=8)),
     ("utils_get_all_metrics", lambda: on_cpu(ut.get_all_metrics, np.eye(3), np.eye(3))),
+    ("graph_louvain_sign", lambda: pt.graph_louvain_sign(f64(3, 3))),
+    ("graph_louvain_sign_seeds_ws", lambda: pt.graph_louvain_sign(f64(2, 3, 3), seeds=[0, (1 << 64) - 1], ws_bytes=144)),
+    ("graph_consensus", lambda: pt.graph_consensus(f64(3, 3), 0.5, reps=2)),
+    ("graph_rewire", lambda: nm.graph_rewire(f64(4, 4))),
+    ("graph_null_model", lambda: nm.graph_null_model(f64(4, 4), seeds=[1, 2], ws_bytes=48)),
+    ("participation_norm", lambda: nm.participation_norm(f64(4, 4), LAB4, reps=2)),
+    ("surrogate_fc", lambda: sg.surrogate_fc(f64(4, 2), [1, 2])),
+    ("fc_surrogate_test", lambda: sg.fc_surrogate_test(f64(4, 2), surr_number=2)),
 ]]
 
 Z3 = np.zeros(64, dtype=complex)
@@ -543,6 +756,66 @@ DOUBLE_ROWS = [
      "welch: x must be a [T][C] or [T][B][N] fp64 device tensor"),
     ("welch_detrend_scaling", lambda: sc.welch(f64(64, 2), detrend="linear", scaling="nope"), NotImplementedError,
      "welch: detrend = 'linear' (only 'constant' and False run on the device)"),
+    ("louvain_sign_qtype_gamma", lambda: pt.graph_louvain_sign(f32(3, 3), seeds=-1, gamma=None, qtype="nope"), ValueError,
+     "graph_louvain_sign: modularity type unknown: qtype 'nope', must be one of " + QT),
+    ("louvain_sign_gamma_seeds", lambda: pt.graph_louvain_sign(f32(3, 3), seeds=-1, gamma=None), ValueError,
+     "graph_louvain_sign: gamma = None, must be a finite number"),
+    ("louvain_sign_seeds_w", lambda: pt.graph_louvain_sign(f32(3, 3), seeds=-1, ws_bytes=1), ValueError,
+     "graph_louvain_sign: " + SEEDS + "-1"),
+    ("louvain_sign_w_ws", lambda: pt.graph_louvain_sign(f32(3, 3), ws_bytes=1), TypeError, "graph_louvain_sign: " + STACK),
+    ("consensus_reps_max_iter", lambda: pt.graph_consensus(f32(3, 3), None, reps=0, seeds=[1], max_iter=0), ValueError,
+     "graph_consensus: reps = 0, must be a positive int"),
+    ("consensus_max_iter_tau", lambda: pt.graph_consensus(f32(3, 3), None, reps=2, seeds=[1], max_iter=0), ValueError,
+     "graph_consensus: max_iter = 0, must be a positive int"),
+    ("consensus_tau_seeds", lambda: pt.graph_consensus(f32(3, 3), None, reps=2, seeds=[1]), ValueError,
+     "graph_consensus: tau = None, must be a finite number"),
+    ("consensus_seeds_value_len", lambda: pt.graph_consensus(f32(3, 3), 0.5, reps=2, seeds=[-1]), ValueError,
+     "graph_consensus: " + SEEDS + "[-1]"),
+    ("consensus_seeds_D", lambda: pt.graph_consensus(f32(3, 3), 0.5, reps=2, seeds=[1]), ValueError,
+     "graph_consensus: seeds must be a sequence of length reps = 2, or None"),
+    ("rewire_seeds_N", lambda: nm.graph_rewire(f64(3, 3), bin_swaps=-1, seeds=-1), ValueError, "graph_rewire: " + SEEDS + "-1"),
+    ("rewire_N_swaps", lambda: nm.graph_rewire(f64(3, 3), bin_swaps=-1, ws_bytes=1), ValueError,
+     "graph_rewire: N = 3, a rewiring takes four distinct nodes: needs N >= 4"),
+    ("rewire_swaps_ws", lambda: nm.graph_rewire(f64(4, 4), bin_swaps=-1, ws_bytes=1), ValueError,
+     "graph_rewire: bin_swaps = -1, must be an int >= 0"),
+    ("null_model_negative_wei_freq", lambda: nm.graph_null_model(f64(3, 3), seeds=-1, wei_freq=2, negative="nope"),
+     ValueError, "graph_null_model: negative = 'nope', must be one of ['reference', 'bct']"),
+    ("null_model_wei_freq_seeds", lambda: nm.graph_null_model(f64(3, 3), seeds=-1, wei_freq=2), ValueError,
+     "graph_null_model: wei_freq = 2, must be a number in [0, 1]"),
+    ("null_model_seeds_N", lambda: nm.graph_null_model(f64(3, 3), seeds=-1), ValueError, "graph_null_model: " + SEEDS + "-1"),
+    ("null_model_N_swaps", lambda: nm.graph_null_model(f64(3, 3), bin_swaps=-1), ValueError,
+     "graph_null_model: N = 3, a rewiring takes four distinct nodes: needs N >= 4"),
+    ("null_model_swaps_ws", lambda: nm.graph_null_model(f64(4, 4), bin_swaps=-1, ws_bytes=1), ValueError,
+     "graph_null_model: bin_swaps = -1, must be an int >= 0"),
+    ("pnorm_reps_max_bytes", lambda: nm.participation_norm(f64(3, 3), LAB4, reps=0, max_bytes=0), ValueError,
+     "participation_norm: reps = 0, must be a positive int"),
+    ("pnorm_max_bytes_seeds", lambda: nm.participation_norm(f64(3, 3), LAB4, reps=2, seeds=[1], max_bytes=0), ValueError,
+     "participation_norm: max_bytes = 0, must be a positive int"),
+    ("pnorm_seeds_negative", lambda: nm.participation_norm(f64(3, 3), LAB4, reps=2, seeds=[1], negative="nope"), ValueError,
+     "participation_norm: seeds must be a sequence of length reps = 2, or None"),
+    ("pnorm_negative_wei_freq", lambda: nm.participation_norm(f64(3, 3), LAB4, reps=2, wei_freq=2, negative="nope"),
+     ValueError, "participation_norm: negative = 'nope', must be one of ['reference', 'bct']"),
+    ("pnorm_wei_freq_N", lambda: nm.participation_norm(f64(3, 3), LAB4, reps=2, wei_freq=2), ValueError,
+     "participation_norm: wei_freq = 2, must be a number in [0, 1]"),
+    ("pnorm_N_swaps", lambda: nm.participation_norm(f64(3, 3), LAB4, reps=2, bin_swaps=-1), ValueError,
+     "participation_norm: N = 3, a rewiring takes four distinct nodes: needs N >= 4"),
+    ("pnorm_swaps_labels", lambda: nm.participation_norm(f64(4, 4), [0], reps=2, bin_swaps=-1), ValueError,
+     "participation_norm: bin_swaps = -1, must be an int >= 0"),
+    ("surrogate_fc_x_seeds", lambda: sg.surrogate_fc(f64(5, 2), [1]), ValueError, "surrogate_fc: L = 5, " + EVEN_L),
+    ("surrogate_test_surr_number_alpha", lambda: sg.fc_surrogate_test(f64(5, 2), surr_number=1, alpha=2, seeds=[1]),
+     ValueError, "fc_surrogate_test: surr_number = 1, must be an int of at least 2"),
+    ("surrogate_test_alpha_seeds", lambda: sg.fc_surrogate_test(f64(5, 2), surr_number=2, alpha=2, seeds=[1]), ValueError,
+     "fc_surrogate_test: alpha = 2, must lie in (0, 1)"),
+    ("surrogate_test_seeds_x", lambda: sg.fc_surrogate_test(f64(5, 2), surr_number=2, seeds=[1], ws_bytes=1), ValueError,
+     "fc_surrogate_test: seeds must be a sequence of surr_number = 2 ints in [0, 2^64), got [1]"),
+    ("surrogate_test_x_ws", lambda: sg.fc_surrogate_test(f64(5, 2), surr_number=2, ws_bytes=1), ValueError,
+     "fc_surrogate_test: L = 5, " + EVEN_L),
+    ("randmio_N_itr", lambda: nmn.randmio_und_signed(np.zeros((3, 3)), -1), ValueError,
+     "randmio_und_signed: N = 3, the device kernel takes 4 <= N <= 96"),
+    ("pcn_degree_N", lambda: nmn.participation_coef_norm(np.zeros((3, 3)), [0], degree="both"), ValueError,
+     "participation_coef_norm: degree 'both', must be 'undirected', 'in' or 'out'"),
+    ("probabilistic_thresholding_conn_y", lambda: sgn.probabilistic_thresholding(np.zeros(3), conn="plv"), KeyError,
+     "'invalid connectivity metric'"),
 ]
 
 
@@ -689,6 +962,36 @@ SIGNATURES = {
         "agreement": "(ci, buffsz=1000)",
         "get_agreement_matrix": "(W, reps=100, tau=0.5, gamma=1, ci=None, B='modularity', seeds=None)",
     },
+    "partition": {
+        "louvain_sign_slot_bytes": "(N)",
+        "graph_louvain_sign": "(w, seeds=0, gamma=1.0, qtype='sta', want_info=False, ws_bytes=None)",
+        "graph_consensus": "(D, tau, reps=1000, seeds=None, max_iter=100)",
+    },
+    "nullmodel": {
+        "null_model_slot_bytes": "(N)",
+        "period_of": "(name, wei_freq)",
+        "graph_rewire": "(w, bin_swaps=5, seeds=0, want_info=False, ws_bytes=None)",
+        "graph_null_model": "(w, seeds=0, bin_swaps=5, wei_freq=0.1, negative='bct', want_stats=False, ws_bytes=None)",
+        "participation_norm": "(w, ci, reps=100, seeds=None, bin_swaps=5, wei_freq=0.1, negative='bct', "
+                              "max_bytes=268435456)",
+    },
+    "surrogate": {
+        "surrogate_slab_bytes": "(N, S)",
+        "surrogate_fc": "(x, seeds)",
+        "fc_surrogate_test": "(x, surr_number=50, alpha=0.05, seeds=None, want_stats=False, ws_bytes=None)",
+    },
+    "partition_np": {
+        "modularity_louvain_und_sign": "(W, gamma=1, qtype='sta', seed=None)",
+        "consensus_und": "(D, tau, reps=1000)",
+    },
+    "nullmodel_np": {
+        "randmio_und_signed": "(R, itr, seed=None)",
+        "null_model_und_sign": "(W, bin_swaps=5, wei_freq=0.1, seed=None)",
+        "participation_coef_norm": "(W, ci, degree='undirected', BA_iters=100)",
+    },
+    "surrogate_np": {
+        "probabilistic_thresholding": "(y, surr_number=50, alpha=0.05, conn='corr')",
+    },
 }
 
 CONSTANTS = {
@@ -744,9 +1047,33 @@ CONSTANTS = {
     "graph_utils": {
         "GRAPH_MAX_N": 96,
     },
+    "partition": {
+        "LOUVAIN_SIGN_QTYPES": ("sta", "pos", "smp", "gja", "neg"),
+        "LOUVAIN_SIGN_SLOTS": 2048,
+    },
+    "nullmodel": {
+        "NULL_MODEL_MIN_N": 4,
+        "NULL_MODEL_SLOTS": 4096,
+        "NULL_MODEL_MAX_PERIOD": 64,
+        "NEGATIVE_MODES": ("reference", "bct"),
+        "PARTICIPATION_NORM_BYTES": 268435456,
+    },
+    "surrogate": {
+        "SURROGATE_MAX_L": 4096,
+        "SURROGATE_WS_CAP": 1073741824,
+    },
+    "partition_np": {
+        "CONSENSUS_MAX_ITER": 100,
+    },
+    "nullmodel_np": {
+        "NULL_MODEL_MIN_N": 4,
+        "NULL_MODEL_MAX_N": 96,
+    },
+    "surrogate_np": {},
 }
 
-MODULES = {"sigchain": sc, "utils": ut, "graph_utils": gu}
+MODULES = {"sigchain": sc, "utils": ut, "graph_utils": gu, "partition": pt, "nullmodel": nm, "surrogate": sg,
+           "partition_np": ptn, "nullmodel_np": nmn, "surrogate_np": sgn}
 
 
 def _public(mod):
