@@ -866,6 +866,70 @@ int wc_graph_null_model(int B, int R, int N, const double* w, int bin_swaps, int
                         const uint64_t* seeds, double* w0, double* r, int32_t* info,
                         void* workspace, size_t ws_bytes, void* stream);
 
+/* Hub organisation of B matrices (wc_hubs.hip): the reference's rich_club_wu (graph_utils.py:2528-2570),
+ * rich_club_wd (:2482-2525), rich_club_bu (:2440-2479), rich_club_bd (:2396-2437), assortativity_wei
+ * (:1869-1926), assortativity_bin (:1808-1866) and score_wu (:2573-2609).  tests/hubs_reference.py
+ * restates this text in numpy.
+ *
+ * All three: w [B][N][N] fp64, 2 <= N <= 96, one workgroup per matrix.  No symmetry is assumed and
+ * the diagonal is taken as given: the expressions are evaluated as the reference writes them.  A
+ * matrix with a NaN or an infinity anywhere has NaN in its fp64 outputs and -1 in its int32 outputs;
+ * no other matrix is affected.  Fixed order, no atomics: a matrix gives the same bits alone as in any
+ * batch.  Every output may be NULL, but not all of them.
+ *
+ * wc_graph_rich_club.  deg_j = the non-zeros of column j (directed == 0: rich_club_wu, degrees_und), plus
+ *   the non-zeros of row j (directed != 0: rich_club_wd, degrees_dir's deg).  K levels are written,
+ *   1 <= K <= N (directed == 0) or 2 N (directed != 0); level index k = 0 .. K-1 stands for the degree
+ *   l = k + 1.
+ *     maxdeg [B]    int32  max_j deg_j, the reference's default klevel
+ *     rw     [B][K] the weighted coefficient: NaN where no node has deg < l (the reference's
+ *                   `continue`); else, over the nodes with deg >= l, Wr = the sum of every entry of the
+ *                   kept submatrix, both triangles and the diagonal, Er = the number of its non-zero
+ *                   entries, and rw = Wr / (the sum of the Er largest of all N^2 entries of w): the first
+ *                   Er of np.sort(w.flat)[::-1], in which zeros and negative entries take their place.
+ *                   No node kept, or none of its entries non-zero: 0 / 0 = NaN.
+ *     rb     [B][K] the binary coefficient ek / (nk (nk - 1)) as IEEE gives it (nk = 0: NaN; nk = 1:
+ *                   NaN or +-inf), over the nodes with deg > l (the reference removes deg <= k + 1)
+ *     nk     [B][K] int32  the number of those nodes
+ *     ek     [B][K] the sum of their submatrix of w as given; the reference does not binarise it
+ *   Sums: with the nodes in descending order of degree, ties by ascending index, the kept nodes are the
+ *   first n; node a's shell, w[a][b] then w[b][a] for the b before it and then w[a][a], is added up
+ *   over b in the order a + 1, a + 2, ... modulo N, the shells in order of a.  The sorted entries
+ *   are added in blocks of 64 (a tree over xor distances 32 .. 1), the blocks and then the rest in order.
+ *
+ * wc_graph_assortativity.  flag 0 takes the edges i < j with w[i][j] > 0 (np.triu(w, 1) > 0), flags 1 .. 4
+ *   every (i, j) with w[i][j] > 0; other flags: WC_EINVAL.  With in = column, out = row, the values a
+ *   of the edge's i and b of its j are
+ *     r_bin [B]  the non-zeros: flag 0 in/in (degrees_und), 1 out/in, 2 in/out, 3 out/out, 4 in/in;
+ *     r_wei [B]  the sums: flag 0 in/in (strengths_und), 1 out/in, 2 in/out, 3 out/out, and flag 4
+ *                in/out, THE SAME AS FLAG 2: the reference's assortativity_wei reads ist[i], ost[j]
+ *                there although its docstring says in/in.  Done as written, and pinned by a test.
+ *   and with E the number of edges
+ *     term1 = sum(a b) / E, term2 = (sum((a + b) / 2) / E)^2, term3 = sum((a^2 + b^2) / 2) / E,
+ *     r = (term1 - term2) / (term3 - term2),
+ *   one rounding per operation in this order; the sums run over j within a row, then over the rows.
+ *   The degree sums are exact, so r_bin is the reference's bits and a regular graph gives its exact
+ *   0 / 0 = NaN.  E = 0: NaN.
+ *
+ * wc_graph_score.  s [B][S] fp64 levels, S >= 1, B S < 2^31.  Per (matrix, level) score_wu's loop:
+ *   the strengths are the column sums of the current matrix, a column added up in row order
+ *   0 .. N-1 (np.sum(axis=0) of a C-ordered matrix); all nodes with 0 < str < s are peeled together,
+ *   their rows and columns going to zero; repeated until no node is peeled.
+ *     member [B][S][N] int32  1 where the node was not peeled
+ *     sn     [B][S]    int32  the nodes with str > 0 at the end
+ *     rounds [B][S]    int32  the passes that peeled a node or more
+ *   The core matrix is w with the rows and columns of the peeled nodes cleared.
+ *
+ * Checked before any device work: B >= 1, 2 <= N <= 96 (more: WC_EUNSUPPORTED), w not NULL, an output
+ * given, K, flag and S in range, s not NULL; fp64 arrays 8-byte, int32 arrays 4-byte aligned; no output
+ * overlapping an input or another output. */
+int wc_graph_rich_club(int B, int N, const double* w, int directed, int K, double* rw, double* rb,
+                       int32_t* nk, double* ek, int32_t* maxdeg, void* stream);
+int wc_graph_assortativity(int B, int N, const double* w, int flag, double* r_wei, double* r_bin,
+                           void* stream);
+int wc_graph_score(int B, int N, int S, const double* w, const double* s, int32_t* member, int32_t* sn,
+                   int32_t* rounds, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -114,6 +114,9 @@ _SIGNATURES = {
     "wc_graph_rewire": (c_int, [c_int, c_int, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "wc_graph_null_model": (c_int, [c_int, c_int, c_int, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz,
                                     c_vp]),
+    "wc_graph_rich_club": (c_int, [c_int, c_int, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "wc_graph_assortativity": (c_int, [c_int, c_int, c_vp, c_int, c_vp, c_vp, c_vp]),
+    "wc_graph_score": (c_int, [c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
 }
 
 

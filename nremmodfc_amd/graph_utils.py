@@ -15,7 +15,8 @@ modularity_louvain_und_sign and consensus_und through partition (partition_np);
 probabilistic_thresholding, the surrogate test that decides which FC entries are
 links at all, through surrogate.fc_surrogate_test (surrogate_np);
 randmio_und_signed, null_model_und_sign and participation_coef_norm through
-nullmodel (nullmodel_np).  torch and
+nullmodel (nullmodel_np); rich_club_wu, rich_club_wd, rich_club_bu, rich_club_bd,
+assortativity_wei, assortativity_bin and score_wu through hubs (hubs_np).  torch and
 the library are imported on first use, so importing this module stays light.
 
 Outside: of the partition search the 'negative_sym' and 'negative_asym'
@@ -23,11 +24,12 @@ objectives (unreachable in the reference, which refuses negative weights
 first), the spectral search of modularity_und (its kci form is
 graph_module_measures' Q), and N > 96; probabilistic_thresholding2, the
 rank-remapped variant of the surrogate test.  The rest of the 2,600-line
-toolbox (rich club, assortativity, the other null models) is analysis outside
-the sweep path.
+toolbox (the other null models) is analysis outside the sweep path.
 """
 import numpy as np
 
+from .hubs_np import (assortativity_bin, assortativity_wei, rich_club_bd, rich_club_bu, rich_club_wd,  # noqa: F401
+                      rich_club_wu, score_wu)  # (wc_hubs.hip)
 from .nullmodel_np import null_model_und_sign, participation_coef_norm, randmio_und_signed  # noqa: F401  (wc_nullmodel.hip)
 from .partition_np import consensus_und, modularity_louvain_und_sign  # noqa: F401  (wc_louvain_sign.hip)
 from .surrogate_np import probabilistic_thresholding  # noqa: F401  (wc_surrogate.hip)
